@@ -18,7 +18,13 @@ SearchForTriangulation(left_i, right_i) of one frame). The sub-batches cycle ove
 (default 8) distinct resident batches, so no sub-batch re-reads the previous one's input.
 value = stereo frames processed by all ranks / max-over-ranks wall time of the K timed steps.
 
-Launch: python bench.py [--gpus N] [--steps K] [--warmup W]. With N > 1 and no torch.distributed
+Launch: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]. A plain
+run sets up, warms up, times the K steps (with the per-kernel dispatch events of --event-every,
+part of the timed region) and prints the line; --full adds, after the timed steps, the oracle check
+of the last sub-batch (parity_bit_exact), the host-boundary rates, the secondary legs and the CPU
+baseline. --dump-outputs writes the last timed sub-batch's outputs as .npy (dump_outputs); the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
+With N > 1 and no torch.distributed
 environment, the script starts torch.distributed.run as a child process (before any GPU call)
 and exits with its status; the driver's own torchrun launch is used as is.
 """
@@ -48,6 +54,15 @@ def parse(argv=None):
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline figure: the oracle check "
+                        "of the last sub-batch, the host cost of enqueueing a sub-batch, the host-boundary rates, "
+                        "the secondary legs and the CPU baseline (each still switched off by its own --no-... "
+                        "option); without it the run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed sub-batch returned to its caller "
+                        "(pipeline.C3Pipeline.to_host: keypoints, descriptors, BowVector, FeatureVector, "
+                        "SearchForTriangulation matches, mvuRight) as DIR/<name>.npy in float32 / float64")
     p.add_argument("--batch", type=int, default=32, help="stereo frames per GPU per sub-batch (C3)")
     p.add_argument("--batches-per-step", type=int, default=1024,
                    help="sub-batches per step: a step is long enough for external samplers to see")
@@ -68,7 +83,9 @@ def parse(argv=None):
                    help="with --no-kernel-events: sub-batches of the untimed pass that times every kernel")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--no-gather", action="store_true")
-    p.add_argument("--no-kernel-events", action="store_true")
+    p.add_argument("--no-kernel-events", action="store_true",
+                   help="no per-kernel dispatch events in the timed region; --full then times every kernel in a "
+                        "short pass of its own, a plain run reports roofline null and no per-kernel figures")
     p.add_argument("--no-legs", action="store_true", help="skip the secondary measurements")
     p.add_argument("--no-parity", action="store_true", help="skip the oracle check of the last sub-batch")
     p.add_argument("--pipeline", type=int, default=0,
@@ -666,13 +683,13 @@ def main():
     # 24 times, the median -- the device queues stay short, so no launch blocks on a full queue (32
     # back to back, rounds 3-5, could fill them: 88-197 us for the same code)
     host_samples = []
-    for _ in range(24):
+    for _ in range(24 if args.full else 0):
         torch.cuda.synchronize()
         th0 = time.perf_counter()
         sub_batch()
         sub_batch()
         host_samples.append((time.perf_counter() - th0) / 2)
-    host_us = float(np.median(host_samples)) * 1e6
+    host_us = float(np.median(host_samples)) * 1e6 if host_samples else None
     torch.cuda.synchronize()
     # timed region: every kernel's launches on every n-th group of sub-batches timed by their own
     # dispatch interval (orbfe_ktimer: start / stop events bound to the dispatch, the interval
@@ -705,7 +722,9 @@ def main():
     barrier()
     t1 = time.perf_counter()
     timed = L.ktimer_read()
-    if not timed:  # --no-kernel-events: a short untimed pass with every kernel timed instead
+    if args.dump_outputs:  # before anything else runs on the pipeline: the last timed sub-batch's outputs
+        dump_outputs(args.dump_outputs, pipe.to_host(pipe.last), rank, world)
+    if not timed and args.full:  # --no-kernel-events: a short untimed pass with every kernel timed instead
         L.ktimer_select(True)
         for _ in range(args.probe_subbatches):
             sub_batch()
@@ -713,8 +732,9 @@ def main():
         L.ktimer_select(False)
         timed, timed_events = L.ktimer_read(), args.probe_subbatches
     corr = {k: (ms - c * kt_overhead * 1e-3, c) for k, (ms, c) in timed.items()}  # overhead off each launch
-    dominant = max(corr, key=lambda k: corr[k][0])
-    watch = [dominant] + (["k_fast"] if dominant != "k_fast" and "k_fast" in timed else [])
+    # (no kernel was timed: --no-kernel-events without --full, which has no pass of its own for them)
+    dominant = max(corr, key=lambda k: corr[k][0]) if corr else None
+    watch = ([dominant] + (["k_fast"] if dominant != "k_fast" and "k_fast" in timed else [])) if corr else []
     elapsed = t1 - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=comm_dev)
@@ -745,8 +765,9 @@ def main():
         if issue is not None:
             r["issue"] = issue
         rooflines.append(r)
-    roof = rooflines[0]
-    roof["dominant_by"] = "device time per sub-batch, every kernel timed on the same sub-batches"
+    roof = rooflines[0] if rooflines else None
+    if roof is not None:
+        roof["dominant_by"] = "device time per sub-batch, every kernel timed on the same sub-batches"
     if len(rooflines) > 1:
         roof["also"] = rooflines[1:]
     algo_frame = pipeline_bytes_per_stereo_frame(geo, counts, B, pipe.n_pairs)
@@ -759,7 +780,7 @@ def main():
         "warmup": args.warmup,
         "ms_per_step": round(1e3 * elapsed / args.steps, 4),
         "host_enqueue_ms_per_step": round(1e3 * (t_enq - t0) / args.steps, 4),
-        "host_us_per_subbatch_unblocked": round(host_us, 1),
+        **({"host_us_per_subbatch_unblocked": round(host_us, 1)} if host_us is not None else {}),
         "launch_graphs": dict(zip(("captures", "replays", "held"), ext.debug_graph_stats())),
         "enqueue": ("one orbfe_c3_run call per sub-batch (include/orbfe_c3.h)" if pipe._c3 is not None
                     else "per-stage library calls from Python (--stage-calls)"),
@@ -804,7 +825,7 @@ def main():
             "achieved_GBps": round(algo_frame * value / world / 1e9, 3),
             "frac_of_peak": round(algo_frame * value / world / 1e9 / HBM_PEAK_GBS, 6),
         },
-        "kernels_us_per_subbatch": {k: round(1e3 * v[0] / timed_events, 2)
+        "kernels_us_per_subbatch": {k: round(1e3 * v[0] / max(timed_events, 1), 2)
                                     for k, v in sorted(corr.items(), key=lambda kv: -kv[1][0])},
         "kernels_us_per_subbatch_what": ("device execution per sub-batch on the timed region's event sub-batches "
                                          "(dispatch-bound events less the timer's per-dispatch overhead, "
@@ -827,7 +848,7 @@ def main():
     if isinstance(g, Gatherer) and args.dump_gather:
         dump_gather(args.dump_gather, g, pipe, rank, world)
     # ---- parity of the last timed sub-batch (every rank checks its own) ----
-    if not args.no_parity:
+    if args.full and not args.no_parity:
         from oracle.c3_check import check_c3
         from oracle.orbref import RefVocabulary
         ref_voc = RefVocabulary.from_table(tree.k, tree.levels, tree.scoring, tree.weighting, tree.parent,
@@ -848,9 +869,9 @@ def main():
                                  "BowVector, FeatureVector, match12")
     if args.rehearse:
         out["rehearsal"] = "N ranks on one GPU over gloo, host-staged: not a measurement"
-    if world > 1 and not args.no_legs:
+    if world > 1 and args.full and not args.no_legs:
         out["legs"] = {"c5_search_local_points": c5_leg(args, world, rank, comm_dev)}
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         # the host-buffer legs use the first handle with the one-handle blur placement; its side
         # work stays on the pipeline's side stream, created before the handles' own streams
         # (measured: 20.7k / 19.6k stereo frames/s on the handle's own side stream, 22.1-22.9k
@@ -868,7 +889,7 @@ def main():
                                                                 pipe.cap, state["cam"]["bf"], state["mb"]),
                            "vocabulary_transform": vocab_leg(args, voc, tree, pipe),
                            "c3_other_pairing": pairing_leg(args, exts, tree, voc, d_img, pstreams, dev)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(host[0], B, H, W, args, tree, state)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -885,7 +906,7 @@ def host_fed_leg(args, steps=3, subbatches=256):
     (ORBextractor.cc:1041-1048, two per stereo Frame, Frame.cc:113-116), so this is the rate a
     host-resident image stream gets; the headline keeps the inputs in HBM."""
     cmd = [sys.executable, os.path.abspath(__file__), "--feed", "host", "--steps", str(steps), "--warmup", "1",
-           "--batches-per-step", str(subbatches), "--no-legs", "--no-cpu", "--event-every", "1000000"]
+           "--batches-per-step", str(subbatches), "--full", "--no-legs", "--no-cpu", "--event-every", "1000000"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     except subprocess.TimeoutExpired:
@@ -916,6 +937,55 @@ def dump_gather(d, g, pipe, rank, world):
     if rank == 0:
         for r, v in enumerate(g.last):
             v.cpu().numpy().tofile(os.path.join(d, f"{r}_gathered.bin"))
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 0xD0C3
+
+
+def dump_outputs(d, h, rank=0, world=1):
+    """--dump-outputs: the last timed sub-batch as its caller receives it (h: C3Pipeline.to_host),
+    one DIR/<name>.npy per output (rank r of several writes rank<r>_<name>.npy), the per-image /
+    per-pair arrays concatenated in image / pair order with their lengths beside them. float32 where
+    every value is exact in it (keypoint fields, descriptor bytes, match indices, mvuRight), float64
+    otherwise (BowVector weights, word and node ids, counts). Over DUMP_MAX_BYTES in all (each of
+    several ranks has an equal share of it), every array of more than 1,024 rows keeps the same
+    seeded sample of its rows, in order."""
+    def cat(parts, dtype, width=None):
+        parts = [np.asarray(p) for p in parts]
+        a = np.concatenate(parts) if parts else np.zeros(0)
+        a = a.astype(dtype)
+        return a.reshape(-1, width) if width else a
+
+    kp = h["keypoints"]
+    fields = ("x", "y", "size", "angle", "response", "octave", "class_id")
+    arrays = {
+        "keypoint_counts": np.array([len(k) for k in kp], np.float64),
+        "keypoints": cat([np.stack([k[f].astype(np.float32) for f in fields], 1) for k in kp], np.float32, len(fields)),
+        "descriptors": cat(h["descriptors"], np.float32, 32),
+        "bow_counts": np.array([len(w) for w, _ in h["bow"]], np.float64),
+        "bow_words": cat([w for w, _ in h["bow"]], np.float64),
+        "bow_weights": cat([t for _, t in h["bow"]], np.float64),
+        "fv_node_counts": np.array([len(i) for i, _, _ in h["fv"]], np.float64),
+        "fv_node_ids": cat([i for i, _, _ in h["fv"]], np.float64),
+        "fv_offsets": cat([o for _, o, _ in h["fv"]], np.float64),
+        "fv_indices": cat([x for _, _, x in h["fv"]], np.float64),
+        "match12": cat(h["match12"], np.float32),
+        "nmatches": np.asarray(h["nmatches"]).astype(np.float64),
+    }
+    if "u_right" in h:
+        arrays["u_right"] = cat(h["u_right"], np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    limit = DUMP_MAX_BYTES // max(world, 1)
+    if total > limit:
+        keep = 0.98 * limit / total
+        for name, a in arrays.items():
+            if len(a) > 1024:
+                rows = np.random.default_rng(DUMP_SEED).choice(len(a), int(len(a) * keep), replace=False)
+                arrays[name] = a[np.sort(rows)]
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, (f"rank{rank}_" if world > 1 else "") + name + ".npy"), np.ascontiguousarray(a))
 
 
 def pipe_depth(args):

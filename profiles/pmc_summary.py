@@ -52,7 +52,7 @@ def main():
                       "traffic_bytes_per_step": round((fb + wb) * per_step)}
     doc = {"workload": {"cols": 1241, "rows": 376, "batch": 32, "pairs": "kf", "stereo": True},
            "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of "
-                     "bench.py --no-cpu --no-legs (profiles/scripts/refresh_profiles.sh; default workload: KeyFrame "
+                     "bench.py --full --no-cpu --no-legs (profiles/scripts/refresh_profiles.sh; default workload: KeyFrame "
                      "pairs, ComputeStereoMatches on); FETCH_SIZE x 2 (gfx950 correction), KiB -> bytes; per launch "
                      "and per sub-batch of 64 images",
            "kernels": kernels}

@@ -5,7 +5,7 @@
 #   LIB_A / LIB_B = liborbfe.so paths (default: the in-tree build; build a variant with
 #     make -C orb_slam2_2021_amd/csrc OUT=../lib_b OBJ=../build_b EXTRA=-D...)
 #   ARGS_A / ARGS_B = extra bench.py arguments per side; BENCH_ARGS = shared ones
-#     (default "--no-cpu --no-legs")
+#     (default "--full --no-cpu --no-legs": the line keeps its oracle check)
 # Each run's JSON line goes to $OUT/<A|B><round>.json; summary.txt holds value, ms_per_step and the
 # per-kernel device time of every run.
 set -o pipefail
@@ -16,7 +16,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for v in A B; do
     lib=LIB_$v
     args=ARGS_$v
-    ORBFE_LIB=${!lib:-$LIB_DEF} timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---no-cpu --no-legs} ${!args} \
+    ORBFE_LIB=${!lib:-$LIB_DEF} timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---full --no-cpu --no-legs} ${!args} \
       > $O/$v$r.json 2> $O/$v$r.err || exit 1
     python - "$O/$v$r.json" "$v$r" >> $O/summary.txt <<'PY' || exit 1
 import json, sys

@@ -4,7 +4,7 @@ set -o pipefail
 mkdir -p gpurun_out/hfpf
 for r in $(seq 1 ${ROUNDS:-2}); do
   for a in ${ARMS:---copies-ahead=0 --copies-ahead=3 --copy-thread}; do
-    timeout -k 10 200 python -u bench.py --feed host --steps 3 --warmup 1 --batches-per-step 256 --no-legs --no-cpu \
+    timeout -k 10 200 python -u bench.py --feed host --steps 3 --warmup 1 --batches-per-step 256 --full --no-legs --no-cpu \
       --event-every 1000000 ${a//,/ } ${EXTRA} > gpurun_out/hfpf/a${a//[^a-z0-9]/}.r$r.log 2>&1 || exit 1
     python - gpurun_out/hfpf/a${a//[^a-z0-9]/}.r$r.log "$a round=$r" >> gpurun_out/hfpf/summary.txt <<'PY' || exit 1
 import json, sys

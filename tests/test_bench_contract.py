@@ -72,6 +72,64 @@ def test_cli_defaults():
     assert a.batches_per_step * a.batch >= 32 * 1024
 
 
+def test_plain_run_is_the_default():
+    """--full is off by default, and the measurements beside the headline figure only run with it."""
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench.parse([]).dump_outputs == "" and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one float32 / float64 .npy per output of a sub-batch, values exact, the same
+    files for the same outputs, and a seeded row sample once the whole exceeds the size limit."""
+    from orb_slam2_2021_amd import _lib as L
+    rng = np.random.default_rng(5)
+    n = [3, 0, 5, 2]
+    kps = []
+    for m in n:
+        k = np.zeros(m, L.KEYPOINT_DTYPE)
+        k["x"], k["y"], k["octave"] = rng.random(m, np.float32), rng.random(m, np.float32), rng.integers(0, 8, m)
+        kps.append(k)
+    h = {"keypoints": kps, "descriptors": [rng.integers(0, 256, (m, 32), np.uint8) for m in n],
+         "bow": [(np.arange(m, dtype=np.uint32) * 400_000, rng.random(m)) for m in n[:2]],
+         "fv": [(np.arange(2, dtype=np.uint32), np.array([0, 1, m], np.int32), np.arange(m, dtype=np.int32))
+                for m in n[:2]],
+         "match12": [rng.integers(-1, 5, m, np.int32) for m in n[:3]], "nmatches": np.array([1, 0, 2], np.int32),
+         "u_right": [rng.random(m, np.float32) for m in n[:2]]}
+    bench.dump_outputs(str(tmp_path / "a"), h)
+    bench.dump_outputs(str(tmp_path / "b"), h)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "keypoints.npy" in names and "u_right.npy" in names
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.tobytes() == b.tobytes(), f
+    a = tmp_path / "a"
+    assert np.load(a / "keypoint_counts.npy").tolist() == n
+    assert np.array_equal(np.load(a / "keypoints.npy")[:, 0], np.concatenate([k["x"] for k in kps]))
+    assert np.array_equal(np.load(a / "keypoints.npy")[:, 5], np.concatenate([k["octave"] for k in kps]))
+    assert np.array_equal(np.load(a / "descriptors.npy"), np.concatenate(h["descriptors"]))
+    assert np.array_equal(np.load(a / "bow_words.npy"), np.concatenate([w for w, _ in h["bow"]]))
+    assert np.array_equal(np.load(a / "bow_weights.npy"), np.concatenate([t for _, t in h["bow"]]))
+    assert np.array_equal(np.load(a / "match12.npy"), np.concatenate(h["match12"]))
+    # over the limit: the large arrays keep a seeded sample of their rows, in order, within the limit
+    saved, bench.DUMP_MAX_BYTES = bench.DUMP_MAX_BYTES, 64 << 10
+    try:
+        big = dict(h, keypoints=[np.zeros(4000, L.KEYPOINT_DTYPE)],
+                   descriptors=[rng.integers(0, 256, (4000, 32), np.uint8)])
+        bench.dump_outputs(str(tmp_path / "c"), big)
+        bench.dump_outputs(str(tmp_path / "d"), big)
+        for r in range(2):  # several ranks share the limit
+            bench.dump_outputs(str(tmp_path / "e"), big, rank=r, world=2)
+    finally:
+        bench.DUMP_MAX_BYTES = saved
+    c = {f: np.load(tmp_path / "c" / f) for f in names}
+    assert sum(v.nbytes for v in c.values()) <= 64 << 10
+    assert 0 < len(c["descriptors.npy"]) < 4000 and len(c["descriptors.npy"]) == len(c["keypoints.npy"])
+    assert all(c[f].tobytes() == np.load(tmp_path / "d" / f).tobytes() for f in names)
+    ranks = sorted(os.listdir(tmp_path / "e"))
+    assert ranks == sorted(f"rank{r}_{f}" for r in range(2) for f in names)
+    assert sum(np.load(tmp_path / "e" / f).nbytes for f in ranks) <= 64 << 10
+
+
 def test_hw_queue_setting():
     # several ranks: RCCL's stream gets a hardware queue of its own beside the four pipeline streams
     assert bench.hw_queue_setting(-1, 1) == 0

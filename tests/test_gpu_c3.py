@@ -123,7 +123,7 @@ def test_bench_host_fed_parity(require_gpu, slots):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--feed", "host", "--input-slots", slots, "--steps", "1",
-           "--warmup", "1", "--batches-per-step", "24", "--no-cpu", "--no-legs", "--event-every", "1000000"]
+           "--warmup", "1", "--batches-per-step", "24", "--full", "--no-cpu", "--no-legs", "--event-every", "1000000"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -119,7 +119,7 @@ def test_bench_gatherer_two_ranks_on_one_gpu(require_gpu, tmp_path, root_share):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rehearse", "--gpus", "2", "--steps", "1",
            "--warmup", "1", "--batches-per-step", "4", "--input-batches", "2", "--probe-subbatches", "2",
-           "--no-cpu", "--no-legs", "--no-parity", "--dump-gather", d, "--root-share", root_share]
+           "--full", "--no-cpu", "--no-legs", "--no-parity", "--dump-gather", d, "--root-share", root_share]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     for rank in range(2):

@@ -1,5 +1,6 @@
-"""Pins the tables and constants the oracle and liborbfe share to the reference's own source text
-(read as text from /root/reference; skipped where it is absent, e.g. on the GPU box):
+"""Pins the tables and constants the oracle and liborbfe share to the reference's own source text,
+as recorded in tests/golden/reference_pins.json (the values this module's readers found in a checkout
+of the reference; `python tests/test_reference_pins.py REFERENCE_DIR` records them again):
 
 * bit_pattern_31_ (ORBextractor.cc:153-411) == orb_pattern31.inc, the table both the oracle and
   the HIP kernels compile;
@@ -9,20 +10,48 @@
 * PATCH_SIZE / HALF_PATCH_SIZE / EDGE_THRESHOLD (ORBextractor.cc:71-73) == the oracle's constants;
 * TH_HIGH / TH_LOW / HISTO_LENGTH (ORBmatcher.cc:37-39) == the oracle's, the HIP matchers' and
   the Python mirror's.
-CPU only; nothing is compiled or run from the reference."""
+CPU only; nothing is compiled or run from the reference, and every recorded value is one the
+repository's own sources must equal. The two tests of the cvstub declarations still read the
+reference's headers as text (needs_reference below)."""
+import json
 import math
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
 
-from oracle import orbref
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/src"
+PINS_PATH = os.path.join(ROOT, "tests", "golden", "reference_pins.json")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present")
+# the two stub-interface tests compare declarations (types, parameter lists, default arguments) with
+# the reference's own headers, which are its program text and are not stored here: they read them
+# as text where a checkout is present and skip where it is not
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference sources not present")
+
+# the umax lines restated by oracle/orbref.cpp and orbfe_extract.hip (whitespace removed)
+UMAX_LINES = ("vmax=cvFloor(HALF_PATCH_SIZE*sqrt(2.f)/2+1)",
+              "intvmin=cvCeil(HALF_PATCH_SIZE*sqrt(2.f)/2)",
+              "constdoublehp2=HALF_PATCH_SIZE*HALF_PATCH_SIZE",
+              "for(v=0;v<=vmax;++v)umax[v]=cvRound(sqrt(hp2-v*v));",
+              "for(v=HALF_PATCH_SIZE,v0=0;v>=vmin;--v){while(umax[v0]==umax[v0+1])++v0;umax[v]=v0;++v0;}")
+
+OBJECT_NAMES = [
+    ("MapPoint.h", ["GetWorldPos", "GetNormal", "Observations", "AddObservation", "GetIndexInKeyFrame",
+                    "IsInKeyFrame", "isBad", "Replace", "GetDescriptor", "UpdateNormalAndDepth", "mTrackProjX",
+                    "mTrackProjY", "mTrackProjXR", "mbTrackInView", "mnTrackScaleLevel", "mTrackViewCos",
+                    "mfMinDistance", "mfMaxDistance", "mMutexPos", "mMutexFeatures"]),
+    ("KeyFrame.h", ["GetPose", "GetCameraCenter", "GetRotation", "GetTranslation", "AddMapPoint", "GetMapPoints",
+                    "GetMapPointMatches", "GetMapPoint", "mfGridElementWidthInv", "mvKeysUn", "mvuRight",
+                    "mDescriptors", "mFeatVec", "mnScaleLevels", "mfLogScaleFactor", "mvScaleFactors",
+                    "mvLevelSigma2", "mnMinX", "mnMaxY", "mvpMapPoints", "mMutexFeatures"]),
+    ("Frame.h", ["fx", "cx", "mb", "mvKeysUn", "mFeatVec", "mvpMapPoints", "mvbOutlier", "mfGridElementWidthInv",
+                 "mTcw", "mnScaleLevels", "mfLogScaleFactor", "mvScaleFactors", "mvLevelSigma2", "mnMinX",
+                 "mnMaxY"]),
+]
+PROTECTED_NAMES = ("mfMinDistance", "mMutexPos")
 
 
 def _strip_comments(s):
@@ -30,8 +59,8 @@ def _strip_comments(s):
     return re.sub(r"//[^\n]*", " ", s)
 
 
-def _ref(name):
-    with open(os.path.join(REF, name)) as f:
+def _read(*parts):
+    with open(os.path.join(*parts)) as f:
         return f.read()
 
 
@@ -39,23 +68,16 @@ def _ints(body):
     return [int(v) for v in re.findall(r"-?\d+", body)]
 
 
-def reference_pattern():
-    src = _strip_comments(_ref("ORBextractor.cc"))
+def reference_pattern(src):
     m = re.search(r"bit_pattern_31_\s*\[\s*256\s*\*\s*4\s*\]\s*=\s*\{(.*?)\}\s*;", src, flags=re.S)
     assert m, "bit_pattern_31_ not found"
     return _ints(m.group(1))
 
 
 def repo_pattern():
-    src = open(os.path.join(ROOT, "orb_slam2_2021_amd", "csrc", "orb_pattern31.inc")).read()
+    src = _read(ROOT, "orb_slam2_2021_amd", "csrc", "orb_pattern31.inc")
     body = _strip_comments(src).split("{", 1)[1].split("}", 1)[0]
     return _ints(body)
-
-
-def test_pattern_equals_reference_text():
-    ref = reference_pattern()
-    assert len(ref) == 1024
-    assert repo_pattern() == ref
 
 
 def _ref_const(src, name):
@@ -64,28 +86,88 @@ def _ref_const(src, name):
     return int(m.group(1))
 
 
-def test_patch_constants_equal_reference_text():
-    src = _strip_comments(_ref("ORBextractor.cc"))
-    ref = {k: _ref_const(src, k) for k in ("PATCH_SIZE", "HALF_PATCH_SIZE", "EDGE_THRESHOLD")}
+def _members(text, names):
+    """(type, name) of each data member declaration `T name;` among `names` in declaration order."""
+    out = []
+    for m in re.finditer(r"^\s*([A-Za-z_][\w:<>, \*]*?)\s*\*?\s*([A-Za-z_]\w*)\s*;", _strip_comments(text), re.M):
+        typ, name = re.sub(r"\s+", " ", m.group(1)).strip(), m.group(2)
+        if name in names and typ != "return":
+            out.append((typ, name))
+    return out
+
+
+def _signatures(text, cls):
+    """Public method declarations `Ret Name(params);` of class `cls`, whitespace-normalised."""
+    body = _strip_comments(text)
+    start = re.search(r"class\s+" + cls + r"\s*\{", body).end()
+    depth, i = 1, start
+    while depth:
+        depth += {"{": 1, "}": -1}.get(body[i], 0)
+        i += 1
+    body = body[start:i - 1]
+    out = set()
+    for m in re.finditer(r"([\w:<>,\s\*&]+?)\b(\w+)\s*\(([^;{)]*(?:\([^)]*\)[^;{)]*)*)\)\s*;", body):
+        out.add((m.group(2), re.sub(r"\s+", "", m.group(3))))
+    return out
+
+
+def _names_found(text, names):
+    return [n for n in names if re.search(r"\b" + n + r"\b", text)]
+
+
+def _protected_found(text):
+    prot = text[text.index("protected:"):]
+    return [n for n in PROTECTED_NAMES if n in prot]
+
+
+def record(ref_dir):
+    """What the tests below compare the repository with, read from a checkout of the reference."""
+    ext = _strip_comments(_read(ref_dir, "src", "ORBextractor.cc"))
+    mat = _strip_comments(_read(ref_dir, "src", "ORBmatcher.cc"))
+    norm = re.sub(r"\s+", "", ext)
+    objects = {}
+    for header, names in OBJECT_NAMES:
+        text = _strip_comments(_read(ref_dir, "include", header))
+        objects[header] = {"names": _names_found(text, names)}
+        if header == "MapPoint.h":
+            objects[header]["protected"] = _protected_found(text)
+    return {
+        "bit_pattern_31": reference_pattern(ext),
+        "extractor_constants": {k: _ref_const(ext, k) for k in ("PATCH_SIZE", "HALF_PATCH_SIZE", "EDGE_THRESHOLD")},
+        "umax_lines_present": [piece in norm for piece in UMAX_LINES],
+        "matcher_constants": {k: _ref_const(mat, k) for k in ("TH_HIGH", "TH_LOW", "HISTO_LENGTH")},
+        "objects": objects,
+    }
+
+
+@pytest.fixture(scope="module")
+def pins():
+    with open(PINS_PATH) as f:
+        return json.load(f)
+
+
+def test_pattern_equals_reference_text(pins):
+    ref = pins["bit_pattern_31"]
+    assert len(ref) == 1024
+    assert repo_pattern() == ref
+
+
+def test_patch_constants_equal_reference_text(pins):
+    ref = pins["extractor_constants"]
     assert ref == {"PATCH_SIZE": 31, "HALF_PATCH_SIZE": 15, "EDGE_THRESHOLD": 19}
-    osrc = open(os.path.join(ROOT, "oracle", "orbref.cpp")).read()
+    osrc = _read(ROOT, "oracle", "orbref.cpp")
     mine = {k: int(re.search(r"const int " + k + r" = (\d+);", osrc).group(1))
             for k in ("kPatchSize", "kHalfPatch", "kEdgeThreshold")}
     assert (mine["kPatchSize"], mine["kHalfPatch"], mine["kEdgeThreshold"]) == \
         (ref["PATCH_SIZE"], ref["HALF_PATCH_SIZE"], ref["EDGE_THRESHOLD"])
 
 
-def test_umax_formula_and_table_equal_reference():
-    src = _strip_comments(_ref("ORBextractor.cc"))
-    norm = re.sub(r"\s+", "", src)
-    # the lines restated by oracle/orbref.cpp and orbfe_extract.hip
-    for piece in ("vmax=cvFloor(HALF_PATCH_SIZE*sqrt(2.f)/2+1)",
-                  "intvmin=cvCeil(HALF_PATCH_SIZE*sqrt(2.f)/2)",
-                  "constdoublehp2=HALF_PATCH_SIZE*HALF_PATCH_SIZE",
-                  "for(v=0;v<=vmax;++v)umax[v]=cvRound(sqrt(hp2-v*v));",
-                  "for(v=HALF_PATCH_SIZE,v0=0;v>=vmin;--v){while(umax[v0]==umax[v0+1])++v0;umax[v]=v0;++v0;}"):
-        assert piece in norm, piece
-    hp = _ref_const(src, "HALF_PATCH_SIZE")
+def test_umax_formula_and_table_equal_reference(pins):
+    from oracle import orbref
+    assert len(pins["umax_lines_present"]) == len(UMAX_LINES)
+    for piece, present in zip(UMAX_LINES, pins["umax_lines_present"]):
+        assert present is True, piece
+    hp = pins["extractor_constants"]["HALF_PATCH_SIZE"]
     f = np.float32(hp) * np.float32(math.sqrt(2.0)) / np.float32(2)  # float arithmetic (sqrt(2.f))
     vmax, vmin = math.floor(f + np.float32(1)), math.ceil(f)
     umax = [0] * (hp + 1)
@@ -101,14 +183,13 @@ def test_umax_formula_and_table_equal_reference():
     assert t["umax"].tolist() == umax
 
 
-def test_matcher_thresholds_equal_reference_text():
-    src = _strip_comments(_ref("ORBmatcher.cc"))
-    ref = {k: _ref_const(src, k) for k in ("TH_HIGH", "TH_LOW", "HISTO_LENGTH")}
+def test_matcher_thresholds_equal_reference_text(pins):
+    ref = pins["matcher_constants"]
     assert ref == {"TH_HIGH": 100, "TH_LOW": 50, "HISTO_LENGTH": 30}
-    o = open(os.path.join(ROOT, "oracle", "orbref_match.h")).read()
+    o = _read(ROOT, "oracle", "orbref_match.h")
     assert re.search(r"TH_HIGH = (\d+), TH_LOW = (\d+), HISTO_LENGTH = (\d+)", o).groups() == \
         (str(ref["TH_HIGH"]), str(ref["TH_LOW"]), str(ref["HISTO_LENGTH"]))
-    h = open(os.path.join(ROOT, "orb_slam2_2021_amd", "csrc", "orbfe_match_internal.h")).read()
+    h = _read(ROOT, "orb_slam2_2021_amd", "csrc", "orbfe_match_internal.h")
     for k, v in ref.items():
         assert re.search(r"#define " + k + r" (\d+)", h).group(1) == str(v), k
     from orb_slam2_2021_amd import ORBmatcher
@@ -116,16 +197,7 @@ def test_matcher_thresholds_equal_reference_text():
         (ref["TH_HIGH"], ref["TH_LOW"], ref["HISTO_LENGTH"])
 
 
-def _members(text, names):
-    """(type, name) of each data member declaration `T name;` among `names` in declaration order."""
-    out = []
-    for m in re.finditer(r"^\s*([A-Za-z_][\w:<>, \*]*?)\s*\*?\s*([A-Za-z_]\w*)\s*;", _strip_comments(text), re.M):
-        typ, name = re.sub(r"\s+", " ", m.group(1)).strip(), m.group(2)
-        if name in names and typ != "return":
-            out.append((typ, name))
-    return out
-
-
+@needs_reference
 def test_adapter_test_stub_declares_the_reference_members():
     """tests/cpp/cvstub/ORBextractor.h (the test-only declaration adapter/ORBextractor_gpu.cc is
     compiled against in tests/cpp/adapter_e2e.cpp) declares the data members of the reference's
@@ -148,21 +220,7 @@ def test_adapter_test_stub_declares_the_reference_members():
         assert sig(ref, pat) == sig(stub, pat), pat
 
 
-def _signatures(text, cls):
-    """Public method declarations `Ret Name(params);` of class `cls`, whitespace-normalised."""
-    body = _strip_comments(text)
-    start = re.search(r"class\s+" + cls + r"\s*\{", body).end()
-    depth, i = 1, start
-    while depth:
-        depth += {"{": 1, "}": -1}.get(body[i], 0)
-        i += 1
-    body = body[start:i - 1]
-    out = set()
-    for m in re.finditer(r"([\w:<>,\s\*&]+?)\b(\w+)\s*\(([^;{)]*(?:\([^)]*\)[^;{)]*)*)\)\s*;", body):
-        out.add((m.group(2), re.sub(r"\s+", "", m.group(3))))
-    return out
-
-
+@needs_reference
 def test_matcher_stub_declares_the_reference_interface():
     """tests/cpp/cvstub/ORBmatcher.h (what adapter/ORBmatcher_gpu.cc is compiled over in
     tests/cpp/matcher_e2e.cpp / matcher_tsan.cpp) declares every public method of the reference's
@@ -176,32 +234,22 @@ def test_matcher_stub_declares_the_reference_interface():
     assert public <= stub, public - stub
 
 
-@pytest.mark.parametrize("header,names", [
-    ("MapPoint.h", ["GetWorldPos", "GetNormal", "Observations", "AddObservation", "GetIndexInKeyFrame",
-                    "IsInKeyFrame", "isBad", "Replace", "GetDescriptor", "UpdateNormalAndDepth", "mTrackProjX",
-                    "mTrackProjY", "mTrackProjXR", "mbTrackInView", "mnTrackScaleLevel", "mTrackViewCos",
-                    "mfMinDistance", "mfMaxDistance", "mMutexPos", "mMutexFeatures"]),
-    ("KeyFrame.h", ["GetPose", "GetCameraCenter", "GetRotation", "GetTranslation", "AddMapPoint", "GetMapPoints",
-                    "GetMapPointMatches", "GetMapPoint", "mfGridElementWidthInv", "mvKeysUn", "mvuRight",
-                    "mDescriptors", "mFeatVec", "mnScaleLevels", "mfLogScaleFactor", "mvScaleFactors",
-                    "mvLevelSigma2", "mnMinX", "mnMaxY", "mvpMapPoints", "mMutexFeatures"]),
-    ("Frame.h", ["fx", "cx", "mb", "mvKeysUn", "mFeatVec", "mvpMapPoints", "mvbOutlier", "mfGridElementWidthInv",
-                 "mTcw", "mnScaleLevels", "mfLogScaleFactor", "mvScaleFactors", "mvLevelSigma2", "mnMinX",
-                 "mnMaxY"]),
-])
-def test_object_stubs_use_the_reference_names(header, names):
+@pytest.mark.parametrize("header,names", OBJECT_NAMES)
+def test_object_stubs_use_the_reference_names(pins, header, names):
     """The cvstub Frame / KeyFrame / MapPoint declare, under the reference's own names, what the matcher
     adapter's packers read (adapter/orbfe_pack.hpp, orbfe_adapter.hpp): each name appears in both the
     reference header and the stub, MapPoint's distances as protected members beside mMutexPos."""
-    with open(os.path.join("/root/reference/include", header)) as f:
-        ref = _strip_comments(f.read())
-    with open(os.path.join(ROOT, "tests", "cpp", "cvstub", header)) as f:
-        stub = _strip_comments(f.read())
+    ref = pins["objects"][header]
+    stub = _strip_comments(_read(ROOT, "tests", "cpp", "cvstub", header))
     for n in names:
-        pat = r"\b" + n + r"\b"
-        assert re.search(pat, ref), (header, n)
-        assert re.search(pat, stub), (header, n)
+        assert n in ref["names"], (header, n)
+        assert re.search(r"\b" + n + r"\b", stub), (header, n)
     if header == "MapPoint.h":
-        for text in (ref, stub):
-            prot = text[text.index("protected:"):]
-            assert "mfMinDistance" in prot and "mMutexPos" in prot
+        for found in (ref["protected"], _protected_found(stub)):
+            assert "mfMinDistance" in found and "mMutexPos" in found
+
+
+if __name__ == "__main__":
+    with open(PINS_PATH, "w") as out:
+        json.dump(record(sys.argv[1]), out, indent=1, sort_keys=True)
+        out.write("\n")
