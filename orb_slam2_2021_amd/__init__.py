@@ -10,8 +10,9 @@ from ._lib import (KEYPOINT_DTYPE, LIB_PATH, LibraryMissing, OrbfeError, ORBFE_M
 from .extractor import ORBextractor, register_host, synth_frame, synth_sequence_frame, unregister_host
 from .frames import (FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
                      LocalMapPoints, MapPointGeometry)
+from .keyframe_database import KeyFrameDatabase, SharingList
 from .matcher import ORBmatcher
 
-__all__ = ["ORBextractor", "ORBmatcher", "Frame", "KeyFrame", "FeatureVector", "LocalMapPoints",
-           "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
+__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Frame", "KeyFrame",
+           "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

@@ -1,5 +1,6 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
-orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h).
+orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
+orbfe_kfdb.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -102,6 +103,18 @@ class c3_config(Structure):
     _fields_ = [("n_images", c_int), ("rows", c_int), ("cols", c_int), ("cap", c_int), ("n_vocab", c_int),
                 ("levelsup", c_int), ("n_stereo", c_int), ("mbf", c_float), ("mb", c_float),
                 ("stereo_on_match", c_int), ("n_pairs", c_int)]
+
+
+class kfdb_query(Structure):  # orbfe_kfdb.h
+    _fields_ = [("mode", c_int), ("n", c_int), ("words", c_void_p), ("weights", c_void_p),
+                ("on_device", c_int), ("d_n", c_void_p), ("stream", c_void_p), ("min_score", c_float),
+                ("excluded", c_void_p), ("n_excluded", c_int)]
+
+
+class kfdb_result(Structure):
+    _fields_ = [("capacity", c_int), ("n_sharing", c_int), ("max_common", c_int), ("min_common", c_int),
+                ("kf_ids", c_void_p), ("common_words", c_void_p), ("scored", c_void_p),
+                ("scores", c_void_p), ("n_candidates", c_int), ("candidates", c_void_p)]
 
 
 # name -> (restype, argtypes)
@@ -261,6 +274,17 @@ _SIGNATURES = {
     "orbfe_c3_finish": (c_int, [c_void_p, c_int, c_void_p]),
     "orbfe_c3_match_stream": (c_void_p, [c_void_p, c_int]),
     "orbfe_c3_destroy": (c_int, [c_void_p]),
+    # orbfe_kfdb.h
+    "orbfe_kfdb_create": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_kfdb_destroy": (c_int, [c_void_p]),
+    "orbfe_kfdb_add": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_void_p, c_int]),
+    "orbfe_kfdb_add_batch_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int, c_void_p]),
+    "orbfe_kfdb_erase": (c_int, [c_void_p, ctypes.c_int64]),
+    "orbfe_kfdb_clear": (c_int, [c_void_p]),
+    "orbfe_kfdb_size": (c_int, [c_void_p, POINTER(c_int)]),
+    "orbfe_kfdb_set_covisible": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int]),
+    "orbfe_kfdb_query": (c_int, [c_void_p, POINTER(kfdb_query), POINTER(kfdb_result)]),
 }
 
 # symbols declared in include/*.h (checked by tests/test_library.py)
