@@ -7,7 +7,11 @@ candidate list, for DetectRelocalizationCandidates and DetectLoopCandidates.
 Shapes: 0 / 1 / 2 / 64 / 65 / 300 keyframes (wave and workgroup boundaries of the sweep, more
 than one pass of the finish workgroup's 64-entry sort floor), BowVectors of 0 / 1 / 63 / 64 / 65 /
 ~1000 words (the sweep's 64-word chunks), a 100-word vocabulary for dense sharing and an
-ORBvoc-shaped one (10^6 words, levelsup 4)."""
+ORBvoc-shaped one (10^6 words, levelsup 4).
+
+Past one key per finish thread: stores of 1,023 .. 16,384 keyframes whose sharing list is the whole
+store (big_store below), so k_kfdb_finish's strided compare-exchange, its candidate emission past
+the first 1,024-entry chunk and the dynamic LDS above 64 KiB all run."""
 import numpy as np
 import pytest
 
@@ -323,3 +327,244 @@ def test_back_to_back_queries(small_voc):
     for g, w in zip(got, want):
         same(g, w)
     assert len({tuple(w[1].kf_ids) for w in want}) > 1
+
+
+# ---- stores past one sort key per finish thread ---------------------------------------------------
+BIG_SIZES = [1023, 1024, 1025, 2049, 8192, 8193, 16384]
+BIG_W = 8                       # max_words of the big stores
+COMMON_WORD = 99                # in every keyframe and in the query: the sharing list is the store
+Q_WORDS = [7, 23, 41, 58, 76, COMMON_WORD]
+Q_WEIGHTS = [0.125, 0.25, 0.125, 0.125, 0.125, 0.25]  # exact in binary, sum 1: a clone scores 1.0f
+
+
+def big_store(n_kf, seed):
+    """Hand-built BowVectors of 1-6 words for `n_kf` keyframes over the 100-word vocabulary.
+
+    A sixth are clones of the query (score exactly 1.0f each) and a sixth near-clones, the query
+    without its smallest word (score exactly 0.875f; their first common word is the query's
+    second, so they sit behind every keyframe holding word 7 in the list). The others hold
+    COMMON_WORD and 0-5 seeded words, each of the query's own words with probability 0.7 and
+    otherwise any word below 99, with weights in [1/128, 3/128]: their score is
+    sum(min(vi, wi)) <= 6 * 3/128 < 0.15. The smallest common word -- the high half of the finish
+    kernel's sort key -- so takes the values 7, 23, 41, 58, 76 and 99, each shared by hundreds of
+    keyframes whose order then rests on the add sequence alone. Returns (ids, words[n, BIG_W]
+    uint32, weights[n, BIG_W] float64, counts int32, mask of clones and near-clones, mask of
+    clones); ids are a seeded permutation, so id order is not add order."""
+    rng = np.random.default_rng(seed)
+    ids = rng.permutation(3 * n_kf)[:n_kf].astype(np.int64)
+    words = np.zeros((n_kf, BIG_W), np.uint32)
+    weights = np.zeros((n_kf, BIG_W), np.float64)
+    counts = np.zeros(n_kf, np.int32)
+    kind = rng.random(n_kf)
+    clone, full = kind < 1.0 / 3.0, kind < 1.0 / 6.0
+    for i in range(n_kf):
+        if full[i]:
+            w, x = Q_WORDS, Q_WEIGHTS
+        elif clone[i]:
+            w, x = Q_WORDS[1:], Q_WEIGHTS[1:]
+        else:
+            k = int(rng.integers(0, 6))
+            pick = set()
+            while len(pick) < k:
+                pick.add(int(rng.choice(Q_WORDS[:5])) if rng.random() < 0.7 else int(rng.integers(0, COMMON_WORD)))
+            w = sorted(pick) + [COMMON_WORD]
+            x = (rng.integers(1, 4, len(w)) / 128.0).tolist()
+        counts[i] = len(w)
+        words[i, :len(w)] = w
+        weights[i, :len(w)] = x
+    return ids, words, weights, counts, clone, full
+
+
+def big_covisibility(rng, ids, scored, clone, full, n_set=300):
+    """Neighbour lists for `n_set` keyframes, kept so that no accumulated score passes 1.15 (every
+    clone and near-clone then clears 0.75 * bestAccScore < 0.8625, and the candidate list is long):
+      - a clone or near-clone entry gets up to 3 unscored neighbours and at most one scored
+        non-clone (< 0.15);
+      - a scored non-clone entry gets one of 8 hub clones first (its pBestKF: several entries name
+        the same hub, which is also a candidate by itself -- the deduplication) and unscored ones.
+    Neighbours are drawn from the whole store, so their list indices lie on either side of every
+    1,024 boundary. Returns {id: [neighbour ids]}."""
+    idx = np.arange(len(ids))
+    unscored, low = idx[~scored], idx[scored & ~clone]
+    hubs = rng.choice(idx[full], min(8, int(full.sum())), replace=False)
+    cov = {}
+    for i in rng.choice(idx[scored], min(n_set, int(scored.sum())), replace=False):
+        nb = rng.choice(unscored, min(int(rng.integers(0, 4)), len(unscored)), replace=False).tolist()
+        if clone[i]:
+            if len(low) and rng.random() < 0.5:
+                nb.insert(int(rng.integers(0, len(nb) + 1)), int(rng.choice(low)))
+        else:
+            nb.insert(0, int(rng.choice(hubs)))
+        nb = [j for j in nb if j != i] + ([10 ** 6 + 1] if rng.random() < 0.2 else [])  # one id not stored
+        cov[int(ids[i])] = [int(ids[j]) if j < len(ids) else int(j) for j in nb]
+    return cov
+
+
+class BigPair(Pair):
+    """A Pair whose product side is filled by add_batch_device from hand-built device arrays."""
+
+    def __init__(self, voc, n_kf):
+        super().__init__(voc, max_keyframes=n_kf, max_words=BIG_W)
+
+    def add_batch(self, ids, words, weights, counts, launches=1):
+        import torch
+        dev = torch.device("cuda", 0)
+        for part in np.array_split(np.arange(len(ids)), launches):
+            if len(part) == 0:
+                continue
+            dw = torch.from_numpy(np.ascontiguousarray(words[part]).view(np.int32)).to(dev)
+            dx = torch.from_numpy(np.ascontiguousarray(weights[part])).to(dev)
+            dn = torch.from_numpy(np.ascontiguousarray(counts[part])).to(dev)
+            torch.cuda.synchronize()
+            self.gpu.add_batch_device(ids[part], dw.data_ptr(), dx.data_ptr(), dn.data_ptr(), BIG_W)
+            for i in part:
+                self.ref.add(int(ids[i]), words[i, :counts[i]].tolist(), weights[i, :counts[i]].tolist())
+
+
+def list_index_of_candidates(want):
+    where = {k: i for i, k in enumerate(want[1].kf_ids)}
+    return [where[c] for c in want[0]]
+
+
+def big_queries(pair, ids):
+    """RELOC, then LOOP at the reference's median score with an excluded set from both halves of
+    the slots, then LOOP at 0 (the low scorers stay in lScoreAndMatch: hubs are named twice).
+    Returns the RELOC answer of the reference."""
+    q = bow_of(Q_WORDS, Q_WEIGHTS)
+    reloc = pair.check(RELOC, q)
+    n = len(ids)
+    excluded = [int(i) for i in ids[:5]] + [int(i) for i in ids[n // 2 - 3:n // 2 + 3]] + [int(i) for i in ids[-5:]]
+    excluded = [i for i in excluded if i in pair.ref.kfs] + [10 ** 6 + 7]
+    loop = pair.check(LOOP, q, median_scored(reloc), excluded)
+    assert not set(excluded) & set(loop[1].kf_ids)
+    pair.check(LOOP, q, 0.0, excluded[:3])
+    return reloc
+
+
+@pytest.mark.parametrize("n_kf", BIG_SIZES)
+def test_big_store(small_voc, n_kf):
+    """The sharing list is the whole store: 1,023 / 1,024 / 1,025 (one key per finish thread, and
+    one more), 2,049 (three keys for some threads, a 4,096-key sort), 8,192 / 8,193 (64 KiB of
+    dynamic LDS, and the first size above it) and 16,384 (the bound: 128 KiB)."""
+    _, voc = small_voc
+    ids, words, weights, counts, clone, full = big_store(n_kf, 5000 + n_kf)
+    pair = BigPair(voc, n_kf)
+    pair.add_batch(ids, words, weights, counts, launches=1 if n_kf != 2049 else 3)
+    assert len(pair.gpu) == n_kf
+    q = bow_of(Q_WORDS, Q_WEIGHTS)
+    dry = pair.ref.DetectLoopCandidates(q.words.tolist(), q.weights.tolist(), 0.0)  # who is scored (no mRelocScore written)
+    scored = np.zeros(n_kf, bool)
+    at = {int(k): i for i, k in enumerate(ids)}
+    for k, f in zip(dry[1].kf_ids, dry[1].scored):
+        scored[at[k]] = f
+    rng = np.random.default_rng(n_kf)
+    cov = big_covisibility(rng, ids, scored, clone, full)
+    for k, v in cov.items():
+        pair.set_covisible(k, v)
+    want = big_queries(pair, ids)
+    assert len(want[1].kf_ids) == n_kf                       # every keyframe shares COMMON_WORD
+    assert len(set(np.asarray(want[1].common_words))) >= 5   # and the first-word key is tied widely
+    where = {k: i for i, k in enumerate(want[1].kf_ids)}
+    crossing = sum(1 for k, v in cov.items() for j in v if j in where and where[k] // 1024 != where[j] // 1024)
+    at_idx = list_index_of_candidates(want)
+    assert len(want[0]) > n_kf // 4
+    if n_kf >= 2049:
+        assert crossing >= 20                                # neighbours across a 1,024 boundary
+    if n_kf >= 2049:  # the emission loop's second chunk runs with s_base carried over from the first
+        assert max(at_idx) >= 1024 and min(at_idx) < 1024
+    # more candidates than one chunk holds: from 8,192 on. At 2,049 a third of the store are clones
+    # and near-clones, about 690 candidates, so only their list indices past 1,024 can be asked for
+    if n_kf >= 8192:
+        assert len(want[0]) > 1024
+    if n_kf != 2049:
+        return
+    # holes, renumbered order positions (more than 2 * max_keyframes adds in all), hi > live count
+    gone = [int(i) for i in ids[::3]]
+    for i in gone:
+        pair.erase(i)
+    back = gone[::2]
+    sel = np.array([at[i] for i in back])
+    for _ in range(6):  # 2,049 + 7 * 342 adds in all: past 4,098
+        pair.add_batch(ids[sel], words[sel], weights[sel], counts[sel])
+        for i in back:
+            pair.erase(i)
+    pair.add_batch(ids[sel], words[sel], weights[sel], counts[sel], launches=2)
+    assert n_kf + 7 * len(back) > 2 * n_kf and len(pair.gpu) == n_kf - len(gone) + len(back) < n_kf
+    for k, v in list(cov.items())[::2]:
+        if k in pair.ref.kfs:
+            pair.set_covisible(k, v)
+    want = big_queries(pair, ids)
+    assert len(want[1].kf_ids) == len(pair.ref) and max(list_index_of_candidates(want)) >= 1024
+
+
+def test_readded_keyframe_has_a_fresh_reloc_score(small_voc):
+    """Keyframe 1 is scored by a RELOC query (mRelocScore = 1.0f), erased and re-added under the
+    same id. In the next RELOC query it shares one word (unscored) and is keyframe 0's neighbour:
+    the accumulation adds the 0.0f of a new keyframe (orbfe_kfdb.h), not the 1.0f of the old one --
+    with the stale score it would be pBestKF and the candidate list would be [1]."""
+    _, voc = small_voc
+    pair = Pair(voc, 4, 100)
+    pair.add(0, bow_of(range(0, 10), [0.1] * 10))
+    pair.add(1, bow_of(range(10, 20), [0.1] * 10))
+    pair.add(2, bow_of([0, 10], [0.5, 0.5]))
+    pair.set_covisible(0, [1])
+    want = pair.check(RELOC, bow_of(range(10, 20), [0.1] * 10))
+    assert want[1].kf_ids == [1, 2] and want[1].scored == [True, False] and want[0] == [1]
+    pair.erase(1)
+    pair.add(1, bow_of(range(10, 20), [0.1] * 10))
+    want = pair.check(RELOC, bow_of(range(0, 11), [0.09] * 10 + [0.1]))
+    assert want[1].kf_ids == [0, 2, 1] and want[1].scored == [True, False, False]
+    assert pair.ref.kfs[1].mRelocScore == 0.0
+    assert want[0] == [0]
+
+
+def test_result_capacity_below_the_sharing_list(small_voc):
+    """orbfe_kfdb_query with room for fewer entries than the sharing list: ORBFE_ERR_CAPACITY, and
+    the next query on the handle answers as usual."""
+    from ctypes import byref
+    from orb_slam2_2021_amd import _lib as L
+    _, voc = small_voc
+    pair = Pair(voc, 8, 100)
+    for i in range(5):
+        pair.add(i, bow_of([3, 10 + i], [0.5, 0.5]))
+    q = bow_of([3, 12], [0.5, 0.5])
+    words, weights = pair.gpu._vec(q)
+    cap = 3
+    arrs = [np.zeros(cap, t) for t in (np.int64, np.int32, np.uint8, np.float32, np.int64)]
+    r = L.kfdb_result(capacity=cap, kf_ids=L.ptr(arrs[0]), common_words=L.ptr(arrs[1]), scored=L.ptr(arrs[2]),
+                      scores=L.ptr(arrs[3]), candidates=L.ptr(arrs[4]))
+    kq = L.kfdb_query(mode=RELOC, n=len(words), words=L.ptr(words), weights=L.ptr(weights), on_device=0,
+                      min_score=0.0, excluded=L.ptr(np.zeros(0, np.int64)), n_excluded=0)
+    assert L.lib().orbfe_kfdb_query(pair.gpu._h, byref(kq), byref(r)) == L.ORBFE_ERR_CAPACITY
+    assert all(not a.any() for a in arrs)  # nothing was written past or into the short arrays
+    # the reference ran no query meanwhile; the failed one assigned mRelocScore as a full one does
+    want = pair.ref.DetectRelocalizationCandidates(q.words.tolist(), q.weights.tolist())
+    assert len(want[1].kf_ids) == 5 > cap
+    pair.check(RELOC, q)
+    pair.check(LOOP, q, 0.0, [1])
+
+
+@pytest.mark.parametrize("d_count,used", [(9, 4), (4, 4), (2, 2), (-3, 0), (-2 ** 31, 0), (2 ** 31 - 1, 4)])
+def test_device_count_is_clamped(small_voc, d_count, used):
+    """query_device's count at d_n is clamped to 0..n as k_kfdb_sweep states: the answer is the
+    reference's on the first `used` words."""
+    import torch
+    _, voc = small_voc
+    pair = Pair(voc, 8, 100)
+    vecs = [([1, 5, 9], [0.3, 0.3, 0.4]), ([5, 9, 20, 30], [0.25] * 4), ([1, 30], [0.5, 0.5]), ([40], [1.0])]
+    for i, (w, x) in enumerate(vecs):
+        pair.add(10 + i, bow_of(w, x))
+    pair.set_covisible(10, [11, 12])
+    words = np.array([1, 5, 9, 30, 40, 41], np.int32)   # the bound n = 4 stops before word 40
+    weights = np.array([0.2, 0.3, 0.3, 0.2, 0.5, 0.5], np.float64)
+    dev = torch.device("cuda", 0)
+    dw, dx = torch.from_numpy(words).to(dev), torch.from_numpy(weights).to(dev)
+    dn = torch.tensor([d_count], dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    for mode in (RELOC, LOOP):
+        got = pair.gpu.query_device(mode, dw.data_ptr(), dx.data_ptr(), 4, d_n=dn.data_ptr(), connected=[13])
+        w, x = words[:used].tolist(), weights[:used].tolist()
+        want = (pair.ref.DetectRelocalizationCandidates(w, x) if mode == RELOC
+                else pair.ref.DetectLoopCandidates(w, x, 0.0, [13]))
+        same(got, want)
+        assert (len(want[1].kf_ids) > 0) == (used > 0)
