@@ -12,7 +12,8 @@ from .frames import (FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFram
                      LocalMapPoints, MapPointGeometry)
 from .keyframe_database import KeyFrameDatabase, SharingList
 from .matcher import ORBmatcher
+from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
-__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Frame", "KeyFrame",
+__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "Frame", "KeyFrame",
            "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

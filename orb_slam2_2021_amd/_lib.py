@@ -1,6 +1,6 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
-orbfe_kfdb.h).
+orbfe_kfdb.h, orbfe_sim3.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -115,6 +115,30 @@ class kfdb_result(Structure):
     _fields_ = [("capacity", c_int), ("n_sharing", c_int), ("max_common", c_int), ("min_common", c_int),
                 ("kf_ids", c_void_p), ("common_words", c_void_p), ("scored", c_void_p),
                 ("scores", c_void_p), ("n_candidates", c_int), ("candidates", c_void_p)]
+
+
+class sim3_solver(Structure):  # orbfe_sim3.h
+    _fields_ = [("n", c_int), ("x3dc1", c_void_p), ("x3dc2", c_void_p), ("sigma2_1", c_void_p),
+                ("sigma2_2", c_void_p), ("k1", c_float * 4), ("k2", c_float * 4), ("fix_scale", c_int),
+                ("min_inliers", c_int), ("max_iterations", c_int), ("probability", c_double),
+                ("n_hyp", c_int), ("rand_idx", c_void_p), ("hyp_t12", c_void_p), ("hyp_t21", c_void_p)]
+
+
+class sim3_result(Structure):
+    _fields_ = [("hyp_capacity", c_int), ("mask_words", c_int), ("n_inliers", c_void_p), ("t12", c_void_p),
+                ("t21", c_void_p), ("r12", c_void_p), ("tr12", c_void_p), ("s12", c_void_p),
+                ("inlier_mask", c_void_p), ("n_evaluated", c_int), ("ransac_max_its", c_int),
+                ("accepted", c_int), ("accepted_inliers", c_int), ("best", c_int), ("best_inliers", c_int),
+                ("no_more", c_int)]
+
+
+class sim3_state(Structure):
+    _fields_ = [("iterations", c_int), ("best_inliers", c_int), ("best", c_int)]
+
+
+class sim3_iterate(Structure):
+    _fields_ = [("mask_words", c_int), ("inlier_mask", c_void_p), ("accepted", c_int), ("t12", c_float * 12),
+                ("no_more", c_int), ("n_inliers", c_int)]
 
 
 # name -> (restype, argtypes)
@@ -285,6 +309,11 @@ _SIGNATURES = {
     "orbfe_kfdb_size": (c_int, [c_void_p, POINTER(c_int)]),
     "orbfe_kfdb_set_covisible": (c_int, [c_void_p, ctypes.c_int64, c_void_p, c_int]),
     "orbfe_kfdb_query": (c_int, [c_void_p, POINTER(kfdb_query), POINTER(kfdb_result)]),
+    # orbfe_sim3.h
+    "orbfe_sim3_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_sim3_destroy": (c_int, [c_void_p]),
+    "orbfe_sim3_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "orbfe_sim3_iterate": (c_int, [c_void_p, c_int, c_int, POINTER(sim3_state), POINTER(sim3_iterate)]),
 }
 
 # symbols declared in include/*.h (checked by tests/test_library.py)
