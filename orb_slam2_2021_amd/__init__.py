@@ -8,12 +8,13 @@ from ._lib import (KEYPOINT_DTYPE, LIB_PATH, LibraryMissing, OrbfeError, ORBFE_M
                    MPF_BAD, MPF_OBSERVED, MPF_OUTLIER, MPF_PRESENT, MPF_SEEN, MPF_SKIP,
                    MPF_TRACK_IN_VIEW)
 from .extractor import ORBextractor, register_host, synth_frame, synth_sequence_frame, unregister_host
-from .frames import (FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
-                     LocalMapPoints, MapPointGeometry)
+from .frames import (DeviceTriKeyFrame, FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
+                     LocalMapPoints, MapPointGeometry, TriKeyFrame)
 from .keyframe_database import KeyFrameDatabase, SharingList
 from .matcher import ORBmatcher
 from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
 __all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "Frame", "KeyFrame",
+           "TriKeyFrame", "DeviceTriKeyFrame",
            "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

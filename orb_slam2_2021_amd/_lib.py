@@ -1,6 +1,6 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
-orbfe_kfdb.h, orbfe_sim3.h).
+orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -139,6 +139,28 @@ class sim3_state(Structure):
 class sim3_iterate(Structure):
     _fields_ = [("mask_words", c_int), ("inlier_mask", c_void_p), ("accepted", c_int), ("t12", c_float * 12),
                 ("no_more", c_int), ("n_inliers", c_int)]
+
+
+class tri_keyframe(Structure):  # orbfe_triangulate.h
+    _fields_ = [("tcw", c_float * 12), ("ow", c_float * 3), ("depth", c_void_p), ("keys_xy", c_void_p)]
+
+
+class tri_pair(Structure):
+    _fields_ = [("kf1", frame_view), ("kf2", frame_view), ("t1", tri_keyframe), ("t2", tri_keyframe),
+                ("match12", c_void_p), ("kf1_n_dev", c_void_p), ("status", c_void_p), ("x3d", c_void_p),
+                ("nnew", c_void_p), ("mark1", c_void_p), ("mark2", c_void_p)]
+
+
+class tri_neighbour(Structure):
+    _fields_ = [("kf", frame_view), ("t", tri_keyframe), ("fv", feature_vector), ("f12", c_float * 9),
+                ("ex", c_float), ("ey", c_float)]
+
+
+# orbfe_triangulate.h: status codes of one match
+TRI_NO_MATCH, TRI_TRIANGULATED, TRI_STEREO1, TRI_STEREO2 = 0, 1, 2, 3
+TRI_REJ_PARALLAX, TRI_REJ_W_ZERO, TRI_REJ_Z1, TRI_REJ_Z2, TRI_REJ_REPROJ1, TRI_REJ_REPROJ2 = -1, -2, -3, -4, -5, -6
+TRI_REJ_DIST_ZERO, TRI_REJ_SCALE, TRI_REJ_UNPROJECT, TRI_REJ_BAD_MATCH, TRI_REJ_BAD_OCTAVE = -7, -8, -9, -10, -11
+TRI_MAX_KEYS, TRI_MAX_KF2_KEYS, TRI_MAX_PAIRS, TRI_MAX_NEIGHBOURS = 8192, 16384, 4096, 64
 
 
 # name -> (restype, argtypes)
@@ -314,6 +336,14 @@ _SIGNATURES = {
     "orbfe_sim3_destroy": (c_int, [c_void_p]),
     "orbfe_sim3_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "orbfe_sim3_iterate": (c_int, [c_void_p, c_int, c_int, POINTER(sim3_state), POINTER(sim3_iterate)]),
+    # orbfe_triangulate.h
+    "orbfe_triangulate_matches": (c_int, [c_void_p, POINTER(frame_view), POINTER(tri_keyframe),
+                                          POINTER(frame_view), POINTER(tri_keyframe), c_void_p, c_void_p,
+                                          c_void_p, POINTER(c_int)]),
+    "orbfe_triangulate_batch_device": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "orbfe_create_new_mappoints_device": (c_int, [c_void_p, POINTER(frame_view), POINTER(tri_keyframe),
+                                                  POINTER(feature_vector), c_int, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # symbols declared in include/*.h (checked by tests/test_library.py)

@@ -1842,6 +1842,7 @@ extern "C" int orbfe_matcher_destroy(orbfe_matcher* m) {
   hipFree(m->arena);
   hipFree(m->d_pairs);
   hipFree(m->d_serial);
+  hipFree(m->d_tri);
   if (m->stream) hipStreamDestroy(m->stream);
   if (m->prof_ev0) hipEventDestroy(m->prof_ev0);
   if (m->prof_ev1) hipEventDestroy(m->prof_ev1);
@@ -1924,15 +1925,21 @@ extern "C" int orbfe_search_for_triangulation_batch_device(orbfe_matcher* m, int
   // fv1.n_nodes bounds the node grid (with fv1_nodes_dev set it must be an upper bound)
   int max_nodes = 1;
   for (int p = 0; p < n_pairs; p++) max_nodes = std::max(max_nodes, pairs[p].fv1.n_nodes);
-  // (max_nodes + 3) / 4 workgroups of node wavefronts + one for the features no node lists +
-  // SFT_BIG_WG for the nodes past the wavefront fixpoint
-  ORBFE_LAUNCH("k_sft_nodes", k_sft_nodes, dim3((max_nodes + 3) / 4 + 1 + SFT_BIG_WG, n_pairs), dim3(256), 0, s,
-               m->d_pairs,
-                     only_stereo ? 1 : 0);
-  ORBFE_LAUNCH("k_sft_finish", k_sft_finish, dim3(n_pairs), dim3(256), 0, s, m->d_pairs, m->check_ori);
+  orbfe_mi::sft_launch(s, m->d_pairs, n_pairs, max_nodes, only_stereo, m->check_ori);
   ORBFE_HIP_CHECK(hipGetLastError());
   return ORBFE_OK;
 }
+
+namespace orbfe_mi {
+void sft_launch(hipStream_t s, const orbfe_sft_pair* d_pairs, int n_pairs, int max_nodes, int only_stereo,
+                int check_ori) {
+  // (max_nodes + 3) / 4 workgroups of node wavefronts + one for the features no node lists +
+  // SFT_BIG_WG for the nodes past the wavefront fixpoint
+  ORBFE_LAUNCH("k_sft_nodes", k_sft_nodes, dim3((max_nodes + 3) / 4 + 1 + SFT_BIG_WG, n_pairs), dim3(256), 0, s,
+               d_pairs, only_stereo ? 1 : 0);
+  ORBFE_LAUNCH("k_sft_finish", k_sft_finish, dim3(n_pairs), dim3(256), 0, s, d_pairs, check_ori);
+}
+}  // namespace orbfe_mi
 
 extern "C" int orbfe_search_for_triangulation(orbfe_matcher* m, const orbfe_frame_view* kf1,
                                               const orbfe_frame_view* kf2,

@@ -43,6 +43,11 @@ struct orbfe_matcher {
   int pairs_cap = 0;
   std::vector<orbfe_sft_pair> pairs_uploaded;  // host copy of d_pairs (skip identical uploads)
   int32_t* d_serial = nullptr;
+  // pair records of the triangulation calls (orbfe_triangulate.hip): device copy and the host
+  // bytes it is uploaded from, which outlive the call that queued the copy
+  uint8_t* d_tri = nullptr;
+  size_t d_tri_bytes = 0;
+  std::vector<uint8_t> tri_host;
   // pinned mirror of the arena: host inputs are staged at their arena offsets and uploaded in one
   // H2D copy per call instead of one pageable copy per array
   uint8_t* pinned = nullptr;
@@ -233,6 +238,12 @@ void sbp_launch_grid(orbfe_matcher* m, const SbpPlan& p, const orbfe_frame_view*
 // round 0 only (candidate cache + first result), for callers that consume the cache
 void sbp_launch_round0(orbfe_matcher* m, const SbpPlan& p, const orbfe_frame_view* F, const orbfe_frame_view& dF,
                        const SbpMode& md);
+
+// k_sft_nodes + k_sft_finish over n_pairs pair records already in device memory (max_nodes: an upper
+// bound of their fv1.n_nodes). orbfe_search_for_triangulation_batch_device after its upload;
+// orbfe_create_new_mappoints_device once per neighbour on records it uploaded in one copy.
+void sft_launch(hipStream_t s, const orbfe_sft_pair* d_pairs, int n_pairs, int max_nodes, int only_stereo,
+                int check_ori);
 
 // PredictScale thresholds (host logf), see orbfe_predict_scale_thresholds
 void predict_scale_table(float log_scale_factor, int nlevels, float* thr);

@@ -135,6 +135,87 @@ class KeyFrame(Frame):
         return v
 
 
+class TriKeyFrame:
+    """What LocalMapping::CreateNewMapPoints reads of a KeyFrame beyond the matcher's view
+    (include/orbfe_triangulate.h): GetPose(), GetCameraCenter(), mvDepth and, optionally, the
+    distorted mvKeys that UnprojectStereo reads (None = mvKeysUn). `kf` is the Frame / KeyFrame."""
+
+    def __init__(self, kf: "Frame", depth: np.ndarray, keys_xy: Optional[np.ndarray] = None,
+                 ow: Optional[np.ndarray] = None):
+        if kf.tcw is None:
+            raise ValueError("kf.tcw (GetPose) is required")
+        self.kf = kf
+        self.depth = np.ascontiguousarray(depth, np.float32).reshape(kf.N)
+        self.keys_xy = None if keys_xy is None else np.ascontiguousarray(keys_xy, np.float32).reshape(kf.N, 2)
+        self.ow = np.ascontiguousarray(camera_center(kf.tcw) if ow is None else ow, np.float32).reshape(3)
+
+    # the restatement in tests/ and callers read these like the KeyFrame's own members
+    def __getattr__(self, name):
+        return getattr(self.__dict__["kf"], name)
+
+    def tri_view(self, depth=None, keys_xy=None) -> L.tri_keyframe:
+        """The C struct; depth / keys_xy override the host arrays (device pointers or tensors)."""
+        t = L.tri_keyframe()
+        for i, x in enumerate(np.asarray(self.kf.tcw, np.float32).reshape(12)):
+            t.tcw[i] = float(x)
+        for i, x in enumerate(self.ow):
+            t.ow[i] = float(x)
+        t.depth = L.ptr(self.depth if depth is None else depth)
+        xy = self.keys_xy if keys_xy is None else keys_xy
+        t.keys_xy = L.ptr(xy) if xy is not None else None
+        return t
+
+    def to_device(self, device) -> "DeviceTriKeyFrame":
+        return DeviceTriKeyFrame(self, device)
+
+
+class DeviceTriKeyFrame:
+    """A TriKeyFrame whose arrays live in HBM (torch tensors), for the device entry points.
+    mp_state is the KeyFrame's writable MapPoint-slot array: the triangulation's marking stores
+    ORBFE_MP_OBSERVED into it and the next SearchForTriangulation reads it."""
+
+    def __init__(self, tk: TriKeyFrame, device):
+        import torch
+        kf = tk.kf
+        self.tk = tk
+        self.N = kf.N
+
+        def up(a):
+            a = np.ascontiguousarray(a)
+            if a.size == 0:
+                a = np.zeros(1, a.dtype if a.dtype.fields is None else np.uint8)
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(device)
+
+        self.keys_un, self.u_right, self.descriptors = up(kf.keys_un), up(kf.u_right), up(kf.descriptors)
+        self.mp_state, self.scale_factors, self.level_sigma2 = up(kf.mp_state), up(kf.scale_factors), up(kf.level_sigma2)
+        self.depth = up(tk.depth)
+        self.keys_xy = up(tk.keys_xy) if tk.keys_xy is not None else None
+        self.fv = None
+        if kf.feat_vec is not None:
+            f = kf.feat_vec
+            self.fv = (up(f.node_ids), up(f.offsets), up(f.indices), len(f.node_ids))
+
+    def view(self) -> L.frame_view:
+        v = self.tk.kf.view()
+        for f in ("keys_un", "u_right", "descriptors", "mp_state", "scale_factors", "level_sigma2"):
+            setattr(v, f, L.ptr(getattr(self, f)))
+        return v
+
+    def tri_view(self) -> L.tri_keyframe:
+        return self.tk.tri_view(self.depth, self.keys_xy)
+
+    def fv_view(self) -> L.feature_vector:
+        if self.fv is None:
+            raise ValueError("the KeyFrame needs feat_vec (mFeatVec)")
+        v = L.feature_vector()
+        v.node_ids, v.offsets, v.indices = L.ptr(self.fv[0]), L.ptr(self.fv[1]), L.ptr(self.fv[2])
+        v.n_nodes = self.fv[3]
+        return v
+
+    def mp_state_host(self) -> np.ndarray:
+        return self.mp_state.cpu().numpy()[:self.N].copy()
+
+
 @dataclass
 class FeatureVector:
     """DBoW2::FeatureVector (node id -> ascending feature indices) as CSR."""

@@ -25,8 +25,8 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 
 from . import _lib as L
-from .frames import (FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
-                     LocalMapPoints, MapPointGeometry, epipole, log_scale_factor)
+from .frames import (DeviceTriKeyFrame, FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
+                     LocalMapPoints, MapPointGeometry, TriKeyFrame, epipole, log_scale_factor)
 
 
 def _mp_count(mps) -> int:
@@ -336,6 +336,70 @@ class ORBmatcher:
             self._h, len(descriptor_sets), L.ptr(offsets), L.ptr(desc), L.ptr(out)),
             "ComputeDistinctiveDescriptors")
         return out[:len(descriptor_sets)]
+
+    # ---- LocalMapping::CreateNewMapPoints' geometry (orbfe_triangulate.h) ---------------------
+    def TriangulateMatches(self, kf1: TriKeyFrame, kf2: TriKeyFrame, match12: np.ndarray,
+                           x3d: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray, int]:
+        """The match loop of CreateNewMapPoints (LocalMapping.cc:290-456) for one KeyFrame pair over
+        host arrays: (status int8 per KF1 keypoint, x3d (N1, 3) float32, nnew). x3d entries whose
+        status is <= 0 keep the value passed in (zeros by default)."""
+        n1 = kf1.kf.N
+        m12 = np.ascontiguousarray(match12, np.int32).reshape(n1)
+        status = np.zeros(max(n1, 1), np.int8)
+        out = (np.zeros((max(n1, 1), 3), np.float32) if x3d is None
+               else np.ascontiguousarray(x3d, np.float32).reshape(n1, 3).copy())
+        v1, v2, t1, t2 = kf1.kf.view(), kf2.kf.view(), kf1.tri_view(), kf2.tri_view()
+        nn = c_int()
+        L.check(self._lib.orbfe_triangulate_matches(self._h, byref(v1), byref(t1), byref(v2), byref(t2),
+                                                    L.ptr(m12) if n1 else None, L.ptr(status), L.ptr(out),
+                                                    byref(nn)), "TriangulateMatches")
+        return status[:n1], out[:n1], nn.value
+
+    def TriangulateBatchDevice(self, pairs, stream=None) -> None:
+        """orbfe_triangulate_batch_device: `pairs` is a ctypes array (or list) of _lib.tri_pair whose
+        pointers are device memory; asynchronous on `stream` (None = the matcher's stream)."""
+        n = len(pairs)
+        if isinstance(pairs, (list, tuple)):
+            pairs = (L.tri_pair * max(n, 1))(*pairs)
+        L.check(self._lib.orbfe_triangulate_batch_device(self._h, n, ctypes.addressof(pairs), L.ptr(stream)),
+                "TriangulateBatchDevice")
+
+    def CreateNewMapPointsDevice(self, kf1: DeviceTriKeyFrame, neighbours, F12s, epipoles, stream=None):
+        """CreateNewMapPoints' neighbour loop (LocalMapping.cc:241-457) on the device: per neighbour
+        SearchForTriangulation(KF1, nb, F12, ., false), the triangulation, and the AddMapPoint marking
+        in both KeyFrames' device mp_state, all on one stream. Returns device tensors
+        (match12 (n_nb, N1) int32, status (n_nb, N1) int8, x3d (n_nb, N1, 3) float32, nmatches (n_nb),
+        nnew (n_nb)); nothing is synchronised."""
+        import torch
+        n_nb, n1 = len(neighbours), kf1.N
+        dev = kf1.mp_state.device
+        shape = (max(n_nb, 1), max(n1, 1))
+        m12 = torch.full(shape, -1, dtype=torch.int32, device=dev)
+        status = torch.zeros(shape, dtype=torch.int8, device=dev)
+        x3d = torch.zeros(shape + (3,), dtype=torch.float32, device=dev)
+        nm = torch.zeros(shape[0], dtype=torch.int32, device=dev)
+        nnew = torch.zeros(shape[0], dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the fills above ran on torch's stream
+        nbs = (L.tri_neighbour * max(n_nb, 1))()
+        for j, nb in enumerate(neighbours):
+            nbs[j].kf, nbs[j].t, nbs[j].fv = nb.view(), nb.tri_view(), nb.fv_view()
+            for k, x in enumerate(np.asarray(F12s[j], np.float32).reshape(9)):
+                nbs[j].f12[k] = float(x)
+            nbs[j].ex, nbs[j].ey = float(epipoles[j][0]), float(epipoles[j][1])
+        v1, t1, f1 = kf1.view(), kf1.tri_view(), kf1.fv_view()
+        L.check(self._lib.orbfe_create_new_mappoints_device(
+            self._h, byref(v1), byref(t1), byref(f1), n_nb, ctypes.addressof(nbs), L.ptr(m12), L.ptr(status),
+            L.ptr(x3d), L.ptr(nm), L.ptr(nnew), L.ptr(stream)), "CreateNewMapPointsDevice")
+        return m12[:n_nb, :n1], status[:n_nb, :n1], x3d[:n_nb, :n1], nm[:n_nb], nnew[:n_nb]
+
+    def stream(self) -> int:
+        """The matcher's hipStream_t (orbfe_matcher_stream)."""
+        return int(self._lib.orbfe_matcher_stream(self._h) or 0)
+
+    def synchronize(self) -> None:
+        """Wait for the matcher's stream."""
+        import torch
+        torch.cuda.ExternalStream(self.stream()).synchronize()
 
     def SearchForTriangulation(self, pKF1: Frame, pKF2: Frame, F12: np.ndarray,
                                bOnlyStereo: bool = False,
