@@ -1,6 +1,6 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
-orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h).
+orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -139,6 +139,37 @@ class sim3_state(Structure):
 class sim3_iterate(Structure):
     _fields_ = [("mask_words", c_int), ("inlier_mask", c_void_p), ("accepted", c_int), ("t12", c_float * 12),
                 ("no_more", c_int), ("n_inliers", c_int)]
+
+
+class pnp_solver(Structure):  # orbfe_pnp.h
+    _fields_ = [("n", c_int), ("p3dw", c_void_p), ("p2d", c_void_p), ("sigma2", c_void_p), ("k", c_float * 4),
+                ("probability", c_double), ("min_inliers", c_int), ("max_iterations", c_int), ("min_set", c_int),
+                ("epsilon", c_float), ("th2", c_float), ("n_hyp", c_int), ("rand_idx", c_void_p)]
+
+
+class pnp_result(Structure):
+    _fields_ = [("hyp_capacity", c_int), ("rec_capacity", c_int), ("mask_words", c_int),
+                ("n_inliers", c_void_p), ("inlier_mask", c_void_p), ("r", c_void_p), ("t", c_void_p),
+                ("tcw", c_void_p), ("n_chosen", c_void_p), ("flags", c_void_p),
+                ("records", c_void_p), ("refined_inliers", c_void_p), ("refined_mask", c_void_p),
+                ("refined_r", c_void_p), ("refined_t", c_void_p), ("refined_tcw", c_void_p),
+                ("refined_n_chosen", c_void_p), ("refined_flags", c_void_p),
+                ("n_records", c_int), ("n_evaluated", c_int), ("ransac_max_its", c_int),
+                ("ransac_min_inliers", c_int), ("ransac_epsilon", c_float),
+                ("accepted", c_int), ("accepted_inliers", c_int), ("best", c_int), ("best_inliers", c_int),
+                ("no_more", c_int)]
+
+
+class pnp_state(Structure):
+    _fields_ = [("iterations", c_int), ("best_inliers", c_int), ("best", c_int)]
+
+
+class pnp_iterate(Structure):
+    _fields_ = [("mask_words", c_int), ("inlier_mask", c_void_p), ("returned", c_int), ("accepted", c_int),
+                ("tcw", c_float * 12), ("no_more", c_int), ("n_inliers", c_int)]
+
+
+PNP_FLAG_SVD_NULL, PNP_FLAG_QR_SINGULAR = 1, 2  # orbfe_pnp.h: deviation flags of one hypothesis
 
 
 class tri_keyframe(Structure):  # orbfe_triangulate.h
@@ -336,6 +367,11 @@ _SIGNATURES = {
     "orbfe_sim3_destroy": (c_int, [c_void_p]),
     "orbfe_sim3_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "orbfe_sim3_iterate": (c_int, [c_void_p, c_int, c_int, POINTER(sim3_state), POINTER(sim3_iterate)]),
+    # orbfe_pnp.h
+    "orbfe_pnp_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_pnp_destroy": (c_int, [c_void_p]),
+    "orbfe_pnp_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "orbfe_pnp_iterate": (c_int, [c_void_p, c_int, c_int, POINTER(pnp_state), POINTER(pnp_iterate)]),
     # orbfe_triangulate.h
     "orbfe_triangulate_matches": (c_int, [c_void_p, POINTER(frame_view), POINTER(tri_keyframe),
                                           POINTER(frame_view), POINTER(tri_keyframe), c_void_p, c_void_p,
