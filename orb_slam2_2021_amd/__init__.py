@@ -13,9 +13,10 @@ from .frames import (DeviceTriKeyFrame, FeatureVector, Frame, KeyFrame, KeyFrame
 from .keyframe_database import KeyFrameDatabase, SharingList
 from .matcher import ORBmatcher
 from .pnp_solver import PnPBatch, PnPsolver
+from .pose_optimization import PoseOptimization, PoseOptimizer
 from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
-__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "Frame", "KeyFrame",
+__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "PoseOptimizer", "PoseOptimization", "Frame", "KeyFrame",
            "TriKeyFrame", "DeviceTriKeyFrame",
            "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

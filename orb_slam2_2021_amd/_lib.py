@@ -1,6 +1,6 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
-orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h).
+orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -170,6 +170,26 @@ class pnp_iterate(Structure):
 
 
 PNP_FLAG_SVD_NULL, PNP_FLAG_QR_SINGULAR = 1, 2  # orbfe_pnp.h: deviation flags of one hypothesis
+
+
+class poseopt_problem(Structure):  # orbfe_poseopt.h
+    _fields_ = [("n", c_int), ("valid", c_void_p), ("xw", c_void_p), ("kp_un", c_void_p), ("u_right", c_void_p),
+                ("inv_sigma2", c_void_p), ("k", c_float * 4), ("bf", c_float), ("tcw", c_float * 12)]
+
+
+class poseopt_round(Structure):
+    _fields_ = [("n_active", c_int), ("iterations", c_int), ("trials", c_int), ("rejected_trials", c_int),
+                ("stop", c_int), ("n_bad", c_int), ("lam", c_double), ("chi2", c_double)]
+
+
+class poseopt_result(Structure):
+    _fields_ = [("mask_words", c_int), ("outlier_mask", c_void_p), ("tcw", c_float * 12),
+                ("pose_q_t", c_double * 7), ("n_initial", c_int), ("n_bad", c_int), ("n_inliers", c_int),
+                ("rounds_run", c_int), ("flags", c_uint32), ("rounds", poseopt_round * 4)]
+
+
+POSEOPT_FLAG_LARGE_STEP, POSEOPT_FLAG_NONFINITE = 1, 2  # orbfe_poseopt.h: deviation flags of one problem
+POSEOPT_STOP_ALL, POSEOPT_STOP_TERMINATE, POSEOPT_STOP_NBAD, POSEOPT_STOP_NO_EDGE = 0, 1, 2, 3
 
 
 class tri_keyframe(Structure):  # orbfe_triangulate.h
@@ -372,6 +392,10 @@ _SIGNATURES = {
     "orbfe_pnp_destroy": (c_int, [c_void_p]),
     "orbfe_pnp_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "orbfe_pnp_iterate": (c_int, [c_void_p, c_int, c_int, POINTER(pnp_state), POINTER(pnp_iterate)]),
+    # orbfe_poseopt.h
+    "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_poseopt_destroy": (c_int, [c_void_p]),
+    "orbfe_poseopt_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # orbfe_triangulate.h
     "orbfe_triangulate_matches": (c_int, [c_void_p, POINTER(frame_view), POINTER(tri_keyframe),
                                           POINTER(frame_view), POINTER(tri_keyframe), c_void_p, c_void_p,
