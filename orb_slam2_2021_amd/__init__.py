@@ -14,9 +14,10 @@ from .keyframe_database import KeyFrameDatabase, SharingList
 from .matcher import ORBmatcher
 from .pnp_solver import PnPBatch, PnPsolver
 from .pose_optimization import PoseOptimization, PoseOptimizer
+from .sim3_optimization import OptimizeSim3, Sim3Optimizer, problem_of_keyframes
 from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
-__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "PoseOptimizer", "PoseOptimization", "Frame", "KeyFrame",
+__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "PoseOptimizer", "PoseOptimization", "Sim3Optimizer", "OptimizeSim3", "problem_of_keyframes", "Frame", "KeyFrame",
            "TriKeyFrame", "DeviceTriKeyFrame",
            "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

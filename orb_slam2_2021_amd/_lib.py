@@ -1,6 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
-orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h).
+orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
+orbfe_optsim3.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -186,6 +187,19 @@ class poseopt_result(Structure):
     _fields_ = [("mask_words", c_int), ("outlier_mask", c_void_p), ("tcw", c_float * 12),
                 ("pose_q_t", c_double * 7), ("n_initial", c_int), ("n_bad", c_int), ("n_inliers", c_int),
                 ("rounds_run", c_int), ("flags", c_uint32), ("rounds", poseopt_round * 4)]
+
+
+class optsim3_problem(Structure):  # orbfe_optsim3.h
+    _fields_ = [("n", c_int), ("valid", c_void_p), ("p3d1c", c_void_p), ("p3d2c", c_void_p), ("kp_un1", c_void_p),
+                ("kp_un2", c_void_p), ("inv_sigma2_1", c_void_p), ("inv_sigma2_2", c_void_p), ("k1", c_float * 4),
+                ("k2", c_float * 4), ("r12", c_float * 9), ("t12", c_float * 3), ("s12", c_float), ("th2", c_float),
+                ("fix_scale", c_int), ("has_kf2", c_int), ("r2w", c_float * 9), ("t2w", c_float * 3)]
+
+
+class optsim3_result(Structure):
+    _fields_ = [("mask_words", c_int), ("removed_mask", c_void_p), ("n_correspondences", c_int), ("n_bad", c_int),
+                ("n_inliers", c_int), ("rounds_run", c_int), ("flags", c_uint32), ("sim3_q_t_s", c_double * 8),
+                ("s12_rt", c_float * 12), ("scw", c_float * 12), ("rounds", poseopt_round * 2)]
 
 
 POSEOPT_FLAG_LARGE_STEP, POSEOPT_FLAG_NONFINITE = 1, 2  # orbfe_poseopt.h: deviation flags of one problem
@@ -396,6 +410,10 @@ _SIGNATURES = {
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),
     "orbfe_poseopt_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    # orbfe_optsim3.h
+    "orbfe_optsim3_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_optsim3_destroy": (c_int, [c_void_p]),
+    "orbfe_optsim3_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # orbfe_triangulate.h
     "orbfe_triangulate_matches": (c_int, [c_void_p, POINTER(frame_view), POINTER(tri_keyframe),
                                           POINTER(frame_view), POINTER(tri_keyframe), c_void_p, c_void_p,
