@@ -1,7 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h).
+orbfe_optsim3.h, orbfe_lba.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -201,6 +201,28 @@ class optsim3_result(Structure):
                 ("n_inliers", c_int), ("rounds_run", c_int), ("flags", c_uint32), ("sim3_q_t_s", c_double * 8),
                 ("s12_rt", c_float * 12), ("scw", c_float * 12), ("rounds", poseopt_round * 2)]
 
+
+class lba_problem(Structure):  # orbfe_lba.h
+    _fields_ = [("n_kf", c_int), ("n_points", c_int), ("n_edges", c_int), ("tcw", c_void_p), ("k", c_void_p),
+                ("bf", c_void_p), ("fixed", c_void_p), ("xw", c_void_p), ("edge_begin", c_void_p), ("edge_kf", c_void_p),
+                ("kp_un", c_void_p), ("u_right", c_void_p), ("inv_sigma2", c_void_p), ("stop_flag", c_void_p),
+                ("stop_at_poll", c_int)]
+
+
+class lba_round(Structure):
+    _fields_ = [("n_active", c_int), ("iterations", c_int), ("trials", c_int), ("rejected_trials", c_int),
+                ("stop", c_int), ("n_flagged", c_int), ("lam", c_double), ("chi2", c_double)]
+
+
+class lba_result(Structure):
+    _fields_ = [("tcw", c_void_p), ("xw", c_void_p), ("mask_words", c_int), ("erase_mask", c_void_p),
+                ("level1_mask", c_void_p), ("n_erase", c_int), ("rounds_run", c_int), ("flags", c_uint32),
+                ("polls", c_int), ("rounds", lba_round * 2)]
+
+
+LBA_MAX_FREE_KF, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 128, 512, 16384, 131072  # orbfe_lba.h
+LBA_FLAG_LARGE_STEP, LBA_FLAG_NONFINITE = 1, 2
+LBA_STOP_ALL, LBA_STOP_TERMINATE, LBA_STOP_NBAD, LBA_STOP_NO_EDGE, LBA_STOP_FLAG = 0, 1, 2, 3, 4
 
 POSEOPT_FLAG_LARGE_STEP, POSEOPT_FLAG_NONFINITE = 1, 2  # orbfe_poseopt.h: deviation flags of one problem
 POSEOPT_STOP_ALL, POSEOPT_STOP_TERMINATE, POSEOPT_STOP_NBAD, POSEOPT_STOP_NO_EDGE = 0, 1, 2, 3
@@ -410,6 +432,10 @@ _SIGNATURES = {
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),
     "orbfe_poseopt_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    # orbfe_lba.h
+    "orbfe_lba_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_lba_destroy": (c_int, [c_void_p]),
+    "orbfe_lba_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
     # orbfe_optsim3.h
     "orbfe_optsim3_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_optsim3_destroy": (c_int, [c_void_p]),
