@@ -1,7 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h, orbfe_lba.h).
+orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -221,6 +221,28 @@ class lba_result(Structure):
 
 
 LBA_MAX_FREE_KF, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 128, 512, 16384, 131072  # orbfe_lba.h
+
+
+class essgraph_problem(Structure):  # orbfe_essgraph.h
+    _fields_ = [("n_vertices", c_int), ("tcw", c_void_p), ("fixed_vertex", c_int), ("fix_scale", c_int),
+                ("n_corrected", c_int), ("corrected_idx", c_void_p), ("corrected_sim3", c_void_p),
+                ("n_noncorrected", c_int), ("noncorrected_idx", c_void_p), ("noncorrected_sim3", c_void_p),
+                ("n_edges", c_int), ("edge_i", c_void_p), ("edge_j", c_void_p), ("edge_kind", c_void_p),
+                ("n_points", c_int), ("xw", c_void_p), ("point_ref", c_void_p)]
+
+
+class essgraph_trace(Structure):
+    _fields_ = [("iterations", c_int), ("trials", c_int), ("rejected_trials", c_int), ("stop", c_int),
+                ("lam", c_double), ("chi2", c_double), ("env_blocks", c_int), ("flags", c_uint32)]
+
+
+class essgraph_result(Structure):
+    _fields_ = [("tcw", c_void_p), ("xw", c_void_p), ("trace", essgraph_trace)]
+
+
+ESSGRAPH_MAX_VERTICES, ESSGRAPH_MAX_EDGES, ESSGRAPH_MAX_ENV_BLOCKS, ESSGRAPH_MAX_POINTS = 8192, 65536, 524288, 1048576
+ESSGRAPH_FLAG_LARGE_STEP, ESSGRAPH_FLAG_NONFINITE = 1, 2
+ESSGRAPH_STOP_ALL, ESSGRAPH_STOP_TERMINATE, ESSGRAPH_STOP_NBAD, ESSGRAPH_STOP_NO_EDGE = 0, 1, 2, 3
 LBA_FLAG_LARGE_STEP, LBA_FLAG_NONFINITE = 1, 2
 LBA_STOP_ALL, LBA_STOP_TERMINATE, LBA_STOP_NBAD, LBA_STOP_NO_EDGE, LBA_STOP_FLAG = 0, 1, 2, 3, 4
 
@@ -436,6 +458,10 @@ _SIGNATURES = {
     "orbfe_lba_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_lba_destroy": (c_int, [c_void_p]),
     "orbfe_lba_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
+    # orbfe_essgraph.h
+    "orbfe_essgraph_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_essgraph_destroy": (c_int, [c_void_p]),
+    "orbfe_essgraph_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
     # orbfe_optsim3.h
     "orbfe_optsim3_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_optsim3_destroy": (c_int, [c_void_p]),

@@ -1,0 +1,517 @@
+// orbfe_essgraph.hip -- Optimizer::OptimizeEssentialGraph on the GPU (include/orbfe_essgraph.h): the
+// pose-graph Levenberg-Marquardt over Sim3 vertices with a sparse LDL^T over the block envelope.
+//
+// The Levenberg control flow (eg_run / eg_optimize of orbfe_essgraph_core.h) runs on the host and reads
+// one EgRec per linearisation and per trial; the stages are kernels on the handle's one stream, each a
+// thread- or lane-per-element call of the core header's functions:
+//   k_eg_vertex_setup  per vertex: vScw, the start estimate, the measurement-side state
+//   k_eg_edge_setup    per edge: the measurement
+//   k_eg_linearize     32 lanes per edge: the 29 error evaluations one per lane, the 7 x 14 Jacobian in
+//                      LDS, the edge's 161 products
+//   k_eg_assemble      64 lanes per block: a diagonal block with b_s, or an off-diagonal block that has
+//                      edges, summed in ascending edge index
+//   k_eg_lambda        per diagonal scalar: + lambda on the copy
+//   k_eg_factor        one workgroup: the right-looking block LDL^T over the envelope (per pivot block:
+//                      its 7 x 7 factorisation, the scaled column below, the trailing updates), then the
+//                      forward and the backward substitution
+//   k_eg_update        per vertex: oplus into the trial estimate
+//   k_eg_chi           per edge: the error at the trial estimates
+//   k_eg_reduce        one wavefront: the total chi2 and computeScale by the 64-lane rule
+//   k_eg_finish        per vertex: [R | t / s]; per point: the two maps
+// No kernel waits on another: the stream orders them. Every index a kernel reads was checked by
+// orbfe_essgraph_solve or built by eg_plan; every loop runs to a count among those.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+#include <vector>
+
+#include "../../include/orbfe_essgraph.h"
+#include "orbfe_device.h"
+#include "orbfe_essgraph_core.h"
+#include "orbfe_ktimer.h"
+
+static_assert(EG_FLAG_LARGE_STEP == ORBFE_ESSGRAPH_FLAG_LARGE_STEP && EG_FLAG_NONFINITE == ORBFE_ESSGRAPH_FLAG_NONFINITE,
+              "flag values");
+static_assert(EG_STOP_ALL == ORBFE_ESSGRAPH_STOP_ALL && EG_STOP_TERMINATE == ORBFE_ESSGRAPH_STOP_TERMINATE &&
+                  EG_STOP_NBAD == ORBFE_ESSGRAPH_STOP_NBAD && EG_STOP_NO_EDGE == ORBFE_ESSGRAPH_STOP_NO_EDGE,
+              "stop codes");
+static_assert(sizeof(EgTrace) == sizeof(orbfe_essgraph_trace_t), "trace layout");
+
+#define EG_BLOCK 128
+#define EG_LIN_LANES 32  // lanes per edge in k_eg_linearize
+#define EG_LIN_EDGES 4   // edges per workgroup
+#define EG_FACTOR_THREADS 1024
+static_assert(EG_STATES <= EG_LIN_LANES, "one state per lane");
+
+__global__ __launch_bounds__(EG_BLOCK) void k_eg_vertex_setup(EgWs w) {
+  const int v = blockIdx.x * EG_BLOCK + threadIdx.x;
+  if (v < w.nv) eg_vertex_setup(w, v);
+}
+
+__global__ __launch_bounds__(EG_BLOCK) void k_eg_edge_setup(EgWs w) {
+  const int e = blockIdx.x * EG_BLOCK + threadIdx.x;
+  if (e < w.ne) eg_edge_setup(w, e);
+}
+
+__global__ __launch_bounds__(EG_LIN_LANES* EG_LIN_EDGES) void k_eg_linearize(EgWs w) {
+  __shared__ double sJ[EG_LIN_EDGES][98];
+  const int g = threadIdx.x / EG_LIN_LANES, lane = threadIdx.x % EG_LIN_LANES;
+  const int e = blockIdx.x * EG_LIN_EDGES + g;
+  const bool on = e < w.ne;
+  if (on && lane < EG_STATES) eg_edge_state(w, e, lane, w.est);
+  __syncthreads();  // the group's 29 errors are in e_state
+  const double* st = w.e_state + (size_t)(on ? e : 0) * EG_STATES * 7;
+  if (on)
+    for (int t = lane; t < 98; t += EG_LIN_LANES) sJ[g][t] = eg_jac(st, t / 14, t % 14);
+  __syncthreads();
+  if (on)
+    for (int idx = lane; idx < EG_EDGE_DOUBLES; idx += EG_LIN_LANES)
+      w.e_prod[EG_EDGE_DOUBLES * (size_t)e + idx] = eg_product(sJ[g], st, idx);
+}
+
+__global__ __launch_bounds__(EG_LANES) void k_eg_assemble(EgWs w) {
+  const int item = blockIdx.x, idx = threadIdx.x;
+  if (item < w.ns) {
+    if (idx < 56) eg_diag_entry(w, item, idx);
+  } else if (idx < 49) {
+    eg_offdiag_entry(w, item - w.ns, idx);
+  }
+}
+
+__global__ __launch_bounds__(EG_BLOCK) void k_eg_lambda(EgWs w, double lambda) {
+  const int t = blockIdx.x * EG_BLOCK + threadIdx.x;
+  if (t < 7 * w.ns) eg_add_lambda(w, t / 7, t % 7, lambda);
+}
+
+// The block order of the scalar rule: an entry takes its updates pivot block by pivot block, inside a
+// block p = 0 .. 6, so in ascending scalar pivot index; it is divided by d_j when column j's block is the
+// pivot. The substitutions visit the blocks in the same ascending (forward) and descending (backward)
+// order. y holds the right-hand side throughout; x is written only after a successful factorisation.
+__global__ __launch_bounds__(EG_FACTOR_THREADS) void k_eg_factor(EgWs w) {
+  __shared__ double sD[49];
+  __shared__ double sd[7];
+  __shared__ int s_fail;
+  const int tid = threadIdx.x, nt = EG_FACTOR_THREADS, ns = w.ns;
+  if (tid == 0) s_fail = 0;
+  __syncthreads();
+  for (int b = 0; b < ns; b++) {
+    double* diag = w.L + ((size_t)w.row_off[b + 1] - 1) * 49;
+    if (tid == 0) {
+      for (int r = 0; r < 7; r++)
+        for (int c = 0; c <= r; c++) sD[7 * r + c] = diag[7 * r + c];
+      for (int p = 0; p < 7 && !s_fail; p++) {
+        const double dp = sD[8 * p];
+        if (!po_finite(dp)) s_fail = 2;
+        else if (dp == 0.0) s_fail = 1;
+        if (s_fail) break;
+        sd[p] = dp;
+        w.d[7 * (size_t)b + p] = dp;
+        for (int r = p + 1; r < 7; r++) sD[7 * r + p] = sD[7 * r + p] / dp;
+        for (int r = p + 1; r < 7; r++) {
+          const double m = sD[7 * r + p] * dp;
+          for (int c = p + 1; c <= r; c++) sD[7 * r + c] = sD[7 * r + c] - m * sD[7 * c + p];
+        }
+      }
+      if (!s_fail)
+        for (int r = 0; r < 7; r++)
+          for (int c = 0; c < r; c++) diag[7 * r + c] = sD[7 * r + c];
+    }
+    __syncthreads();
+    if (s_fail) {  // the same value in every thread
+      if (tid == 0) eg_fail(w, s_fail == 2 ? EG_FLAG_NONFINITE : 0u);
+      return;
+    }
+    const int c0 = w.col_begin[b], nr = w.col_begin[b + 1] - c0;
+    for (int t = tid; t < nr * 7; t += nt) {  // the column below: one scalar row per thread
+      const int s = w.col_row[c0 + t / 7];
+      double* row = w.L + ((size_t)w.row_off[s] + (b - w.row_first[s])) * 49 + 7 * (t % 7);
+      double v[7];
+#pragma unroll
+      for (int c = 0; c < 7; c++) v[c] = row[c];
+#pragma unroll
+      for (int c = 0; c < 7; c++) {
+        double a = v[c];
+#pragma unroll
+        for (int p = 0; p < 7; p++)
+          if (p < c) a = a - (v[p] * sd[p]) * sD[7 * c + p];
+        v[c] = a / sd[c];
+      }
+#pragma unroll
+      for (int c = 0; c < 7; c++) row[c] = v[c];
+    }
+    __syncthreads();
+    const long long items = (long long)nr * nr * 49;  // the trailing blocks (a, bb), bb <= a, both rows of the column
+    for (long long t = tid; t < items; t += nt) {
+      const int a = (int)(t / (nr * 49)), rem = (int)(t % (nr * 49)), bb = rem / 49, idx = rem % 49, r = idx / 7, c = idx % 7;
+      if (bb > a || (bb == a && c > r)) continue;
+      const int sa = w.col_row[c0 + a], sb = w.col_row[c0 + bb];
+      const double* La = w.L + ((size_t)w.row_off[sa] + (b - w.row_first[sa])) * 49 + 7 * r;
+      const double* Lb = w.L + ((size_t)w.row_off[sb] + (b - w.row_first[sb])) * 49 + 7 * c;
+      double* dst = w.L + ((size_t)w.row_off[sa] + (sb - w.row_first[sa])) * 49 + idx;
+      double x = *dst;
+#pragma unroll
+      for (int p = 0; p < 7; p++) x = x - (La[p] * sd[p]) * Lb[p];
+      *dst = x;
+    }
+    __syncthreads();
+  }
+  const int n = 7 * ns;
+  for (int i = tid; i < n; i += nt) w.y[i] = w.b[i];
+  __syncthreads();
+  for (int b = 0; b < ns; b++) {  // forward: y_i -= L_ik y_k, k ascending
+    const double* diag = w.L + ((size_t)w.row_off[b + 1] - 1) * 49;
+    double* yb = w.y + 7 * (size_t)b;
+    if (tid == 0)
+      for (int r = 1; r < 7; r++) {
+        double v = yb[r];
+        for (int p = 0; p < r; p++) v = v - diag[7 * r + p] * yb[p];
+        yb[r] = v;
+      }
+    __syncthreads();
+    const int c0 = w.col_begin[b], nr = w.col_begin[b + 1] - c0;
+    for (int t = tid; t < nr * 7; t += nt) {
+      const int s = w.col_row[c0 + t / 7], r = t % 7;
+      const double* row = w.L + ((size_t)w.row_off[s] + (b - w.row_first[s])) * 49 + 7 * r;
+      double v = w.y[7 * (size_t)s + r];
+#pragma unroll
+      for (int p = 0; p < 7; p++) v = v - row[p] * yb[p];
+      w.y[7 * (size_t)s + r] = v;
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < n; i += nt) w.y[i] = w.y[i] / w.d[i];
+  __syncthreads();
+  for (int s = ns - 1; s >= 0; s--) {  // backward: x_i -= L_ki x_k, k descending
+    const double* rowblk = w.L + (size_t)w.row_off[s] * 49;
+    const int nb = s - w.row_first[s];
+    double* ys = w.y + 7 * (size_t)s;
+    if (tid == 0)
+      for (int r = 6; r >= 1; r--) {
+        const double xr = ys[r];
+        for (int c = 0; c < r; c++) ys[c] = ys[c] - rowblk[(size_t)nb * 49 + 7 * r + c] * xr;
+      }
+    __syncthreads();
+    for (int t = tid; t < nb * 7; t += nt) {
+      const int cb = t / 7, cc = t % 7;
+      const double* blk = rowblk + (size_t)cb * 49;
+      double* dst = w.y + 7 * (size_t)(w.row_first[s] + cb) + cc;
+      double v = *dst;
+#pragma unroll
+      for (int r = 6; r >= 0; r--) v = v - blk[7 * r + cc] * ys[r];
+      *dst = v;
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < n; i += nt) w.x[i] = w.y[i];
+}
+
+__global__ __launch_bounds__(EG_BLOCK) void k_eg_update(EgWs w) {
+  const int v = blockIdx.x * EG_BLOCK + threadIdx.x;
+  if (v < w.nv) eg_update_vertex(w, v);
+}
+
+__global__ __launch_bounds__(EG_BLOCK) void k_eg_chi(EgWs w) {
+  const int e = blockIdx.x * EG_BLOCK + threadIdx.x;
+  if (e < w.ne) eg_edge_chi(w, e, w.tri);
+}
+
+__global__ __launch_bounds__(EG_LANES) void k_eg_reduce(EgWs w, int mode, double lambda) {
+  double part[2];
+  eg_reduce_lane(w, threadIdx.x, mode, lambda, part);
+#pragma unroll
+  for (int stride = EG_LANES / 2; stride >= 1; stride >>= 1) {
+    part[0] = part[0] + __shfl_down(part[0], stride);
+    part[1] = part[1] + __shfl_down(part[1], stride);
+  }
+  if (threadIdx.x == 0) w.rec->chi = part[0], w.rec->scale = part[1];
+}
+
+__global__ __launch_bounds__(EG_BLOCK) void k_eg_finish(EgWs w) {
+  const size_t i = (size_t)blockIdx.x * EG_BLOCK + threadIdx.x;
+  if (i < (size_t)w.np) eg_finish_point(w, (int)i);
+  else if (i - w.np < (size_t)w.nv) eg_finish_vertex(w, (int)(i - w.np));
+}
+
+// ------------------------------------------------------------------------------------------
+// host
+
+struct orbfe_essgraph {
+  int device = -1;
+  int max_v = 0, max_e = 0, max_blk = 0, max_p = 0;
+  hipStream_t stream = nullptr;
+  uint8_t* d_pool = nullptr;
+  size_t pool_bytes = 0;
+  EgRec* h_rec = nullptr;  // pinned
+  EgWs w;                  // device pointers, sized for the handle's bounds
+};
+
+static size_t eg_al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// carves the device pool; with base == nullptr only the size is computed
+static size_t eg_carve(orbfe_essgraph* h, uint8_t* base) {
+  size_t off = 0;
+  const size_t nv = h->max_v, ne = h->max_e, nb = h->max_blk, np = h->max_p;
+  EgWs& w = h->w;
+  auto take = [&](size_t bytes) {
+    uint8_t* p = base ? base + off : nullptr;
+    off += eg_al(bytes);
+    return p;
+  };
+#define EG_TAKE(field, type, count) w.field = reinterpret_cast<type*>(take(sizeof(type) * (count)))
+  EG_TAKE(tcw, const float, 12 * nv);
+  EG_TAKE(corr_of_v, const int, nv);
+  EG_TAKE(nonc_of_v, const int, nv);
+  EG_TAKE(corr, const double, 8 * nv);
+  EG_TAKE(nonc, const double, 8 * nv);
+  EG_TAKE(e_i, const int, ne);
+  EG_TAKE(e_j, const int, ne);
+  EG_TAKE(e_kind, const uint8_t, ne);
+  EG_TAKE(xw, const float, 3 * np);
+  EG_TAKE(p_ref, const int, np);
+  EG_TAKE(slot_of_v, const int, nv);
+  EG_TAKE(v_of_slot, const int, nv);
+  EG_TAKE(ve_begin, const int, nv + 1);
+  EG_TAKE(ve_edge, const int, 2 * ne);
+  EG_TAKE(row_first, const int, nv);
+  EG_TAKE(row_off, const int, nv + 1);
+  EG_TAKE(ob_begin, const int, ne + 1);
+  EG_TAKE(ob_pos, const int, ne);
+  EG_TAKE(ob_edge, const int, ne);
+  EG_TAKE(col_begin, const int, nv + 1);
+  EG_TAKE(col_row, const int, nb);
+  EG_TAKE(scw, double, 8 * nv);
+  EG_TAKE(mst, double, 8 * nv);
+  EG_TAKE(est, double, 8 * nv);
+  EG_TAKE(tri, double, 8 * nv);
+  EG_TAKE(meas, double, 8 * ne);
+  EG_TAKE(e_state, double, EG_STATES * 7 * ne);
+  EG_TAKE(e_chi, double, ne);
+  EG_TAKE(e_prod, double, EG_EDGE_DOUBLES * ne);
+  EG_TAKE(H, double, 49 * nb);
+  EG_TAKE(L, double, 49 * nb);
+  EG_TAKE(b, double, 7 * nv);
+  EG_TAKE(d, double, 7 * nv);
+  EG_TAKE(y, double, 7 * nv);
+  EG_TAKE(x, double, 7 * nv);
+  EG_TAKE(out_tcw, float, 12 * nv);
+  EG_TAKE(out_xw, float, 3 * np);
+  EG_TAKE(rec, EgRec, 1);
+#undef EG_TAKE
+  return off;
+}
+
+extern "C" int orbfe_essgraph_create(int device, int max_vertices, int max_edges, int max_env_blocks, int max_points,
+                                     orbfe_essgraph** out) {
+  if (!out) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_create: bad argument");
+  *out = nullptr;
+  if (max_vertices < 1 || max_vertices > ORBFE_ESSGRAPH_MAX_VERTICES || max_edges < 1 || max_edges > ORBFE_ESSGRAPH_MAX_EDGES ||
+      max_env_blocks < 1 || max_env_blocks > ORBFE_ESSGRAPH_MAX_ENV_BLOCKS || max_points < 0 ||
+      max_points > ORBFE_ESSGRAPH_MAX_POINTS)
+    return orbfe_set_error(ORBFE_ERR_ARG,
+                           "orbfe_essgraph_create: max_vertices in 1..8192, max_edges in 1..65536, max_env_blocks in "
+                           "1..524288, max_points in 0..1048576");
+  orbfe_essgraph* h = new orbfe_essgraph();
+  memset(&h->w, 0, sizeof(h->w));
+  h->max_v = max_vertices, h->max_e = max_edges, h->max_blk = max_env_blocks, h->max_p = max_points;
+  if (device < 0) {
+    *out = h;
+    return ORBFE_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    delete h;
+    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_essgraph_create: no such HIP device");
+  }
+  h->device = device;
+  h->pool_bytes = eg_carve(h, nullptr);
+  auto fail = [&](hipError_t e, const char* what) {
+    const int st = orbfe_set_hip_error(e, what);
+    orbfe_essgraph_destroy(h);
+    return st;
+  };
+#define EG_TRY(expr)                              \
+  do {                                            \
+    hipError_t _e = (expr);                       \
+    if (_e != hipSuccess) return fail(_e, #expr); \
+  } while (0)
+  EG_TRY(hipSetDevice(device));
+  EG_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  EG_TRY(hipMalloc(&h->d_pool, h->pool_bytes));
+  EG_TRY(hipHostMalloc(&h->h_rec, sizeof(EgRec), hipHostMallocDefault));
+#undef EG_TRY
+  eg_carve(h, h->d_pool);
+  *out = h;
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_essgraph_destroy(orbfe_essgraph* h) {
+  if (!h) return ORBFE_OK;
+  if (h->device >= 0) {
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    hipFree(h->d_pool);
+    if (h->h_rec) hipHostFree(h->h_rec);
+    if (h->stream) hipStreamDestroy(h->stream);
+  }
+  delete h;
+  return ORBFE_OK;
+}
+
+namespace {
+inline unsigned eg_grid(size_t n) { return (unsigned)((n + EG_BLOCK - 1) / EG_BLOCK); }
+
+// eg_run's backend over the handle's device workspace
+struct EgDevBackend {
+  orbfe_essgraph* h;
+  EgWs w;
+
+  template <class T>
+  int up(const T* dst, const T* src, size_t count) {
+    if (count == 0) return ORBFE_OK;
+    ORBFE_HIP_CHECK(hipMemcpyAsync(const_cast<T*>(dst), src, sizeof(T) * count, hipMemcpyHostToDevice, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));  // the source may be pageable and short-lived
+    return ORBFE_OK;
+  }
+
+  int start(const EgIn& in, const EgPlan& P) {
+    w = h->w;
+    w.nv = in.nv, w.ne = in.ne, w.ns = P.ns, w.nblk = (int)P.nblk, w.nob = P.nob, w.np = in.np;
+    w.fix_scale = in.fix_scale, w.fixed = in.fixed;
+    int st;
+#define EG_UP(dst, src, count) \
+  if ((st = up(dst, src, count)) != ORBFE_OK) return st
+    EG_UP(w.tcw, in.tcw, 12 * (size_t)in.nv);
+    EG_UP(w.corr_of_v, P.corr_of_v.data(), P.corr_of_v.size());
+    EG_UP(w.nonc_of_v, P.nonc_of_v.data(), P.nonc_of_v.size());
+    EG_UP(w.corr, in.corr, 8 * (size_t)in.ncorr);
+    EG_UP(w.nonc, in.nonc, 8 * (size_t)in.nnonc);
+    EG_UP(w.e_i, in.e_i, (size_t)in.ne);
+    EG_UP(w.e_j, in.e_j, (size_t)in.ne);
+    EG_UP(w.e_kind, in.e_kind, (size_t)in.ne);
+    EG_UP(w.xw, in.xw, 3 * (size_t)in.np);
+    EG_UP(w.p_ref, in.p_ref, (size_t)in.np);
+    EG_UP(w.slot_of_v, P.slot_of_v.data(), P.slot_of_v.size());
+    EG_UP(w.v_of_slot, P.v_of_slot.data(), P.v_of_slot.size());
+    EG_UP(w.ve_begin, P.ve_begin.data(), P.ve_begin.size());
+    EG_UP(w.ve_edge, P.ve_edge.data(), P.ve_edge.size());
+    EG_UP(w.row_first, P.row_first.data(), P.row_first.size());
+    EG_UP(w.row_off, P.row_off.data(), P.row_off.size());
+    EG_UP(w.ob_begin, P.ob_begin.data(), P.ob_begin.size());
+    EG_UP(w.ob_pos, P.ob_pos.data(), P.ob_pos.size());
+    EG_UP(w.ob_edge, P.ob_edge.data(), P.ob_edge.size());
+    EG_UP(w.col_begin, P.col_begin.data(), P.col_begin.size());
+    EG_UP(w.col_row, P.col_row.data(), P.col_row.size());
+#undef EG_UP
+    if (w.ns > 0) ORBFE_HIP_CHECK(hipMemsetAsync(w.x, 0, sizeof(double) * 7 * (size_t)w.ns, h->stream));
+    if (w.nv > 0) ORBFE_LAUNCH("k_eg_vertex_setup", k_eg_vertex_setup, dim3(eg_grid(w.nv)), dim3(EG_BLOCK), 0, h->stream, w);
+    if (w.ne > 0) ORBFE_LAUNCH("k_eg_edge_setup", k_eg_edge_setup, dim3(eg_grid(w.ne)), dim3(EG_BLOCK), 0, h->stream, w);
+    return ORBFE_OK;
+  }
+
+  int read_rec(EgRec* out) {
+    ORBFE_HIP_CHECK(hipGetLastError());
+    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_rec, w.rec, sizeof(EgRec), hipMemcpyDeviceToHost, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    *out = *h->h_rec;
+    return ORBFE_OK;
+  }
+
+  int linearize(EgRec* out) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(EgRec), h->stream));
+    ORBFE_LAUNCH("k_eg_linearize", k_eg_linearize, dim3((w.ne + EG_LIN_EDGES - 1) / EG_LIN_EDGES),
+                 dim3(EG_LIN_LANES * EG_LIN_EDGES), 0, h->stream, w);
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.H, 0, sizeof(double) * 49 * (size_t)w.nblk, h->stream));
+    ORBFE_LAUNCH("k_eg_assemble", k_eg_assemble, dim3(w.ns + w.nob), dim3(EG_LANES), 0, h->stream, w);
+    ORBFE_LAUNCH("k_eg_reduce", k_eg_reduce, dim3(1), dim3(EG_LANES), 0, h->stream, w, 0, 0.0);
+    return read_rec(out);
+  }
+
+  int trial(double lambda, EgRec* out) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(EgRec), h->stream));
+    ORBFE_HIP_CHECK(hipMemcpyAsync(w.L, w.H, sizeof(double) * 49 * (size_t)w.nblk, hipMemcpyDeviceToDevice, h->stream));
+    ORBFE_LAUNCH("k_eg_lambda", k_eg_lambda, dim3(eg_grid(7 * (size_t)w.ns)), dim3(EG_BLOCK), 0, h->stream, w, lambda);
+    ORBFE_LAUNCH("k_eg_factor", k_eg_factor, dim3(1), dim3(EG_FACTOR_THREADS), 0, h->stream, w);
+    ORBFE_LAUNCH("k_eg_update", k_eg_update, dim3(eg_grid(w.nv)), dim3(EG_BLOCK), 0, h->stream, w);
+    ORBFE_LAUNCH("k_eg_chi", k_eg_chi, dim3(eg_grid(w.ne)), dim3(EG_BLOCK), 0, h->stream, w);
+    ORBFE_LAUNCH("k_eg_reduce", k_eg_reduce, dim3(1), dim3(EG_LANES), 0, h->stream, w, 1, lambda);
+    return read_rec(out);
+  }
+
+  int accept() {  // discardTop: the trial estimates become the accepted ones
+    double* t = w.est;
+    w.est = w.tri, w.tri = t;
+    return ORBFE_OK;
+  }
+
+  int finish(float* tcw, float* xw) {
+    ORBFE_LAUNCH("k_eg_finish", k_eg_finish, dim3(eg_grid((size_t)w.np + w.nv)), dim3(EG_BLOCK), 0, h->stream, w);
+    ORBFE_HIP_CHECK(hipGetLastError());
+    ORBFE_HIP_CHECK(hipMemcpyAsync(tcw, w.out_tcw, sizeof(float) * 12 * (size_t)w.nv, hipMemcpyDeviceToHost, h->stream));
+    if (w.np > 0)
+      ORBFE_HIP_CHECK(hipMemcpyAsync(xw, w.out_xw, sizeof(float) * 3 * (size_t)w.np, hipMemcpyDeviceToHost, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    return ORBFE_OK;
+  }
+};
+}  // namespace
+
+// the boundary: everything a kernel will use as an index
+static int eg_check(const orbfe_essgraph* h, const orbfe_essgraph_problem_t* p, const orbfe_essgraph_result_t* r) {
+  if (p->n_vertices < 1 || p->n_edges < 0 || p->n_points < 0 || p->n_corrected < 0 || p->n_noncorrected < 0)
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: a count below its minimum");
+  if (p->n_vertices > ORBFE_ESSGRAPH_MAX_VERTICES || p->n_edges > ORBFE_ESSGRAPH_MAX_EDGES || p->n_points > ORBFE_ESSGRAPH_MAX_POINTS)
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: problem above the hard caps");
+  if (p->n_vertices > h->max_v || p->n_edges > h->max_e || p->n_points > h->max_p)
+    return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_essgraph_solve: problem above the handle's bounds");
+  if (p->n_corrected > p->n_vertices || p->n_noncorrected > p->n_vertices)
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: more map entries than vertices");
+  if (!p->tcw || !r->tcw || (p->n_corrected > 0 && (!p->corrected_idx || !p->corrected_sim3)) ||
+      (p->n_noncorrected > 0 && (!p->noncorrected_idx || !p->noncorrected_sim3)) ||
+      (p->n_edges > 0 && (!p->edge_i || !p->edge_j || !p->edge_kind)) || (p->n_points > 0 && (!p->xw || !p->point_ref || !r->xw)))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: null array");
+  const int nv = p->n_vertices;
+  if (p->fixed_vertex < 0 || p->fixed_vertex >= nv) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: fixed_vertex out of range");
+  for (int m = 0; m < 2; m++) {
+    const int n = m ? p->n_noncorrected : p->n_corrected;
+    const int* idx = m ? p->noncorrected_idx : p->corrected_idx;
+    std::vector<uint8_t> seen(nv, 0);
+    for (int k = 0; k < n; k++) {
+      if (idx[k] < 0 || idx[k] >= nv) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: a map's vertex index out of range");
+      if (seen[idx[k]]) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: a keyframe listed twice in a map");
+      seen[idx[k]] = 1;
+    }
+  }
+  for (int e = 0; e < p->n_edges; e++) {
+    if (p->edge_i[e] < 0 || p->edge_i[e] >= nv || p->edge_j[e] < 0 || p->edge_j[e] >= nv)
+      return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: edge vertex index out of range");
+    if (p->edge_i[e] == p->edge_j[e]) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: an edge with i == j");
+    if (p->edge_kind[e] > 1) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: edge kind above 1");
+  }
+  for (int q = 0; q < p->n_points; q++)
+    if (p->point_ref[q] < 0 || p->point_ref[q] >= nv) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: point_ref out of range");
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_essgraph_solve(orbfe_essgraph* h, const orbfe_essgraph_problem_t* p, orbfe_essgraph_result_t* r) {
+  if (!h || !p || !r) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_essgraph_solve: bad argument");
+  int st = eg_check(h, p, r);
+  if (st != ORBFE_OK) return st;
+  EgIn in = {p->n_vertices, p->fixed_vertex, p->fix_scale ? 1 : 0, p->tcw, p->n_corrected, p->corrected_idx, p->corrected_sim3,
+             p->n_noncorrected, p->noncorrected_idx, p->noncorrected_sim3, p->n_edges, p->edge_i, p->edge_j, p->edge_kind,
+             p->n_points, p->xw, p->point_ref};
+  EgPlan plan;
+  eg_plan_envelope(in, &plan);
+  if (plan.nblk > h->max_blk) return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_essgraph_solve: envelope above max_env_blocks");
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "essential graph optimizer is host-only (device < 0)");
+  eg_plan_rest(in, &plan);
+  EgOut o;
+  ORBFE_HIP_CHECK(hipSetDevice(h->device));
+  EgDevBackend b = {h, h->w};
+  st = eg_run(b, in, plan, &o);
+  if (st != ORBFE_OK) return st;
+  memcpy(r->tcw, o.tcw.data(), sizeof(float) * o.tcw.size());
+  if (p->n_points > 0) memcpy(r->xw, o.xw.data(), sizeof(float) * o.xw.size());
+  memcpy(&r->trace, &o.trace, sizeof(r->trace));
+  return ORBFE_OK;
+}
