@@ -1,9 +1,9 @@
 // orbfe_essgraph.hip -- Optimizer::OptimizeEssentialGraph on the GPU (include/orbfe_essgraph.h): the
 // pose-graph Levenberg-Marquardt over Sim3 vertices with a sparse LDL^T over the block envelope.
 //
-// The Levenberg control flow (eg_run / eg_optimize of orbfe_essgraph_core.h) runs on the host and reads
-// one EgRec per linearisation and per trial; the stages are kernels on the handle's one stream, each a
-// thread- or lane-per-element call of the core header's functions:
+// The Levenberg control flow (eg_run of orbfe_essgraph_core.h over lm_host_optimize of orbfe_lm_core.h) runs
+// on the host and reads one LmRec per linearisation and per trial; the stages are kernels on the handle's
+// one stream, each a thread- or lane-per-element call of the core header's functions:
 //   k_eg_vertex_setup  per vertex: vScw, the start estimate, the measurement-side state
 //   k_eg_edge_setup    per edge: the measurement
 //   k_eg_linearize     32 lanes per edge: the 29 error evaluations one per lane, the 7 x 14 Jacobian in
@@ -31,10 +31,10 @@
 #include "orbfe_essgraph_core.h"
 #include "orbfe_ktimer.h"
 
-static_assert(EG_FLAG_LARGE_STEP == ORBFE_ESSGRAPH_FLAG_LARGE_STEP && EG_FLAG_NONFINITE == ORBFE_ESSGRAPH_FLAG_NONFINITE,
+static_assert(LM_FLAG_LARGE_STEP == ORBFE_ESSGRAPH_FLAG_LARGE_STEP && LM_FLAG_NONFINITE == ORBFE_ESSGRAPH_FLAG_NONFINITE,
               "flag values");
-static_assert(EG_STOP_ALL == ORBFE_ESSGRAPH_STOP_ALL && EG_STOP_TERMINATE == ORBFE_ESSGRAPH_STOP_TERMINATE &&
-                  EG_STOP_NBAD == ORBFE_ESSGRAPH_STOP_NBAD && EG_STOP_NO_EDGE == ORBFE_ESSGRAPH_STOP_NO_EDGE,
+static_assert(LM_STOP_ALL == ORBFE_ESSGRAPH_STOP_ALL && LM_STOP_TERMINATE == ORBFE_ESSGRAPH_STOP_TERMINATE &&
+                  LM_STOP_NBAD == ORBFE_ESSGRAPH_STOP_NBAD && LM_STOP_NO_EDGE == ORBFE_ESSGRAPH_STOP_NO_EDGE,
               "stop codes");
 static_assert(sizeof(EgTrace) == sizeof(orbfe_essgraph_trace_t), "trace layout");
 
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(EG_FACTOR_THREADS) void k_eg_factor(EgWs w) {
     }
     __syncthreads();
     if (s_fail) {  // the same value in every thread
-      if (tid == 0) eg_fail(w, s_fail == 2 ? EG_FLAG_NONFINITE : 0u);
+      if (tid == 0) lm_fail(w.rec, s_fail == 2 ? LM_FLAG_NONFINITE : 0u);
       return;
     }
     const int c0 = w.col_begin[b], nr = w.col_begin[b + 1] - c0;
@@ -242,7 +242,7 @@ struct orbfe_essgraph {
   hipStream_t stream = nullptr;
   uint8_t* d_pool = nullptr;
   size_t pool_bytes = 0;
-  EgRec* h_rec = nullptr;  // pinned
+  LmRec* h_rec = nullptr;  // pinned
   EgWs w;                  // device pointers, sized for the handle's bounds
 };
 
@@ -296,7 +296,7 @@ static size_t eg_carve(orbfe_essgraph* h, uint8_t* base) {
   EG_TAKE(x, double, 7 * nv);
   EG_TAKE(out_tcw, float, 12 * nv);
   EG_TAKE(out_xw, float, 3 * np);
-  EG_TAKE(rec, EgRec, 1);
+  EG_TAKE(rec, LmRec, 1);
 #undef EG_TAKE
   return off;
 }
@@ -338,7 +338,7 @@ extern "C" int orbfe_essgraph_create(int device, int max_vertices, int max_edges
   EG_TRY(hipSetDevice(device));
   EG_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   EG_TRY(hipMalloc(&h->d_pool, h->pool_bytes));
-  EG_TRY(hipHostMalloc(&h->h_rec, sizeof(EgRec), hipHostMallocDefault));
+  EG_TRY(hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
 #undef EG_TRY
   eg_carve(h, h->d_pool);
   *out = h;
@@ -409,16 +409,16 @@ struct EgDevBackend {
     return ORBFE_OK;
   }
 
-  int read_rec(EgRec* out) {
+  int read_rec(LmRec* out) {
     ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_rec, w.rec, sizeof(EgRec), hipMemcpyDeviceToHost, h->stream));
+    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_rec, w.rec, sizeof(LmRec), hipMemcpyDeviceToHost, h->stream));
     ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
     *out = *h->h_rec;
     return ORBFE_OK;
   }
 
-  int linearize(EgRec* out) {
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(EgRec), h->stream));
+  int linearize(LmRec* out) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LmRec), h->stream));
     ORBFE_LAUNCH("k_eg_linearize", k_eg_linearize, dim3((w.ne + EG_LIN_EDGES - 1) / EG_LIN_EDGES),
                  dim3(EG_LIN_LANES * EG_LIN_EDGES), 0, h->stream, w);
     ORBFE_HIP_CHECK(hipMemsetAsync(w.H, 0, sizeof(double) * 49 * (size_t)w.nblk, h->stream));
@@ -427,8 +427,8 @@ struct EgDevBackend {
     return read_rec(out);
   }
 
-  int trial(double lambda, EgRec* out) {
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(EgRec), h->stream));
+  int trial(double lambda, LmRec* out) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LmRec), h->stream));
     ORBFE_HIP_CHECK(hipMemcpyAsync(w.L, w.H, sizeof(double) * 49 * (size_t)w.nblk, hipMemcpyDeviceToDevice, h->stream));
     ORBFE_LAUNCH("k_eg_lambda", k_eg_lambda, dim3(eg_grid(7 * (size_t)w.ns)), dim3(EG_BLOCK), 0, h->stream, w, lambda);
     ORBFE_LAUNCH("k_eg_factor", k_eg_factor, dim3(1), dim3(EG_FACTOR_THREADS), 0, h->stream, w);

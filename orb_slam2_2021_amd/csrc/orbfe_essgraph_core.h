@@ -4,11 +4,12 @@
 // setLambda, OptimizationAlgorithmLevenberg with setUserLambdaInit, SparseOptimizer's optimize / push /
 // pop / update) as host/device inline functions over one workspace of plain arrays (EgWs). The kernels of
 // orbfe_essgraph.hip call the per-element functions with one thread or lane each; EgHostBackend below
-// loops the same functions on the host; eg_optimize is the Levenberg control flow, on the host for both.
+// loops the same functions on the host; eg_run drives orbfe_lm_core.h's Levenberg control flow, on the host for both.
 // Used by orbfe_essgraph.hip and tests/cpp/essgraph_core_main.cpp; tests/essgraph_ref.py is the same code
 // in Python. Not part of the C ABI. The quaternion rules, po_sincos, os_exp and the Sim3 functions of
-// orbfe_poseopt_core.h and orbfe_optsim3_core.h are reused unedited; every operation is an IEEE double
-// + - * / sqrt, rounded separately (-ffp-contract=off). "EIGEN:" marks a restated Eigen rule.
+// orbfe_poseopt_core.h and orbfe_optsim3_core.h are reused; the flag and stop codes, the record (LmRec),
+// the host group and po_finite are orbfe_lm_core.h's. Every operation is an IEEE double + - * / sqrt,
+// rounded separately (-ffp-contract=off). "EIGEN:" marks a restated Eigen rule.
 //
 // Summation (the rule that defines the numbers):
 //   per vertex   H_ii and b_i run over the vertex's incident edges in ascending edge index from +0.0;
@@ -21,19 +22,14 @@
 // Every loop is capped by a count the host has checked; every index read from memory was checked by the
 // host (orbfe_essgraph_solve) or built by it (eg_plan).
 #pragma once
-#include "orbfe_optsim3_core.h"
+#include "orbfe_lm_core.h"
+#include "orbfe_optsim3_core.h"  // Sim3: OsSim3, os_sim3_*, os_oplus, os_exp, po_sincos, the quaternion rules
 
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #define EG_LANES 64
-#define EG_FLAG_LARGE_STEP 1u /* == ORBFE_ESSGRAPH_FLAG_LARGE_STEP */
-#define EG_FLAG_NONFINITE 2u  /* == ORBFE_ESSGRAPH_FLAG_NONFINITE */
-#define EG_STOP_ALL 0
-#define EG_STOP_TERMINATE 1
-#define EG_STOP_NBAD 2
-#define EG_STOP_NO_EDGE 3
 #define EG_STATES 29        /* the estimates, then 2 vertices x 7 dimensions x (+delta, -delta) */
 #define EG_EDGE_DOUBLES 161 /* Ji^T Ji 49, Jj^T Jj 49, Ji^T Jj 49, b_i 7, b_j 7 */
 #define EG_MAX_ITER 20
@@ -250,13 +246,6 @@ PO_HD inline double eg_chi2(const double* e) {
   return s;
 }
 
-// What the host reads per linearisation (chi) and per trial (chi, scale, fail, flags).
-struct EgRec {
-  double chi, scale;
-  int32_t fail;
-  uint32_t flags;
-};
-
 struct EgTrace {
   int32_t iterations, trials, rejected_trials, stop;
   double lambda, chi2;
@@ -308,26 +297,8 @@ struct EgWs {
   double* x;  // [ns * 7] the increment of the last successful solve
   float* out_tcw;  // [nv * 12]
   float* out_xw;   // [np * 3]
-  EgRec* rec;
+  LmRec* rec;
 };
-
-PO_HD inline void eg_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (v) atomicOr(p, v);
-#else
-  *p |= v;
-#endif
-}
-
-PO_HD inline void eg_fail(const EgWs& w, uint32_t flag) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  atomicOr(reinterpret_cast<uint32_t*>(&w.rec->fail), 1u);
-  if (flag) atomicOr(&w.rec->flags, flag);
-#else
-  w.rec->fail = 1;
-  w.rec->flags |= flag;
-#endif
-}
 
 // ---- setup --------------------------------------------------------------------------------------------
 // Optimizer.cc:812-847: vScw and the start estimate; the state the kind-1 measurements are taken from
@@ -468,7 +439,7 @@ PO_HD inline void eg_update_vertex(const EgWs& w, int v) {
   os_oplus(u, w.fix_scale != 0, S, &o, &flags);
   w.x[7 * (size_t)s + 6] = u[6];
   os_store_state(w.tri + 8 * (size_t)v, o);
-  eg_or(&w.rec->flags, flags);
+  lm_or(&w.rec->flags, flags);
 }
 
 PO_HD inline void eg_edge_chi(const EgWs& w, int e, const double* est) {
@@ -627,88 +598,30 @@ inline void eg_plan_rest(const EgIn& in, EgPlan* P) {
     for (int c = P->row_first[s]; c < s; c++) P->col_row[cat[c]++] = s;
 }
 
-// SparseOptimizer::optimize(20) with OptimizationAlgorithmLevenberg::solve and setUserLambdaInit(1e-16).
-// A backend B supplies linearize, trial, accept; each returns 0 or an error status that ends the run.
-template <class B>
-inline int eg_optimize(B& b, int n_edges, EgTrace* tr) {
-  EgTrace r = {0, 0, 0, EG_STOP_ALL, 0.0, 0.0, tr->env_blocks, 0};
-  int st = 0;
-  if (n_edges == 0) {
-    r.stop = EG_STOP_NO_EDGE;  // _ivMap.size() == 0: optimize() returns -1 without a step
-    *tr = r;
-    return 0;
-  }
-  double lambda = 0.0, current = 0.0, ni = 2.0;
-  int nbad = 0;
-  for (int i = 0; i < EG_MAX_ITER; i++) {
-    r.iterations++;
-    EgRec rec;
-    if ((st = b.linearize(&rec))) return st;
-    const double ini = rec.chi;
-    current = ini;
-    if (i == 0) {
-      lambda = 1e-16;  // computeLambdaInit returns the user's value
-      ni = 2.0;
-      nbad = 0;
-    }
-    double rho = 0.0;
-    int qmax = 0;
-    do {
-      if ((st = b.trial(lambda, &rec))) return st;
-      r.flags |= rec.flags;
-      double temp = rec.chi;
-      if (rec.fail) temp = DBL_MAX;  // ok2 == false
-      rho = current - temp;
-      rho = rho / (rec.scale + 1e-3);
-      r.trials++;
-      if (rho > 0 && po_finite(temp)) {
-        const double y = 2 * rho - 1;
-        double alpha = 1.0 - y * y * y;  // deviation: pow(2 * rho - 1, 3) as x * x * x
-        alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;
-        const double factor = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;
-        lambda = lambda * factor;
-        ni = 2.0;
-        current = temp;
-        if ((st = b.accept())) return st;  // discardTop
-      } else {
-        lambda = lambda * ni;
-        ni = ni * 2;
-        r.rejected_trials++;  // pop: the accepted estimates stand
-      }
-      qmax++;
-    } while (rho < 0 && qmax < 10);
-    if (qmax == 10 || rho == 0) {
-      r.stop = EG_STOP_TERMINATE;
-      break;
-    }
-    if ((ini - current) * 1e3 < ini) nbad++;
-    else nbad = 0;
-    if (nbad >= 3) {
-      r.stop = EG_STOP_NBAD;
-      break;
-    }
-  }
-  r.lambda = lambda, r.chi2 = current;
-  *tr = r;
-  return 0;
-}
-
-// Optimizer.cc:784-1048 after the caller's gather. B also supplies start and finish.
+// Optimizer.cc:784-1048 after the caller's gather: SparseOptimizer::optimize(20) by orbfe_lm_core.h's
+// lm_host_optimize with setUserLambdaInit(1e-16) and no stop flag. A backend B supplies start, linearize,
+// trial, accept and finish; each returns 0 or an error status that ends the run.
 template <class B>
 inline int eg_run(B& b, const EgIn& in, const EgPlan& P, EgOut* o) {
   o->tcw.assign(12 * (size_t)in.nv, 0.0f), o->xw.assign(3 * (size_t)in.np, 0.0f);
-  memset(&o->trace, 0, sizeof(o->trace));
-  o->trace.env_blocks = (int)P.nblk;
+  const EgTrace none = {0, 0, 0, LM_STOP_NO_EDGE, 0.0, 0.0, (int)P.nblk, 0};
+  o->trace = none;
   int st = 0;
   if ((st = b.start(in, P))) return st;
-  if ((st = eg_optimize(b, in.ne, &o->trace))) return st;
+  if (in.ne > 0) {  // else _ivMap.size() == 0: optimize() returns -1 without a step
+    LmTrace t;
+    LmNoPoll poll;
+    if ((st = lm_host_optimize(b, EG_MAX_ITER, 1e-16, poll, &t))) return st;
+    const EgTrace r = {t.iterations, t.trials, t.rejected_trials, t.stop, t.lambda, t.chi2, (int)P.nblk, t.flags};
+    o->trace = r;
+  }
   return b.finish(o->tcw.data(), o->xw.data());
 }
 
 // The workspace in host memory, every stage a loop over the per-element functions
 struct EgHostBackend {
   EgWs w;
-  EgRec rec;
+  LmRec rec;
   std::vector<double> scw, mst, est, tri, meas, e_state, e_chi, e_prod, H, L, b, d, y, x;
   std::vector<float> out_tcw, out_xw;
 
@@ -743,7 +656,7 @@ struct EgHostBackend {
     rec.chi = part[0][0], rec.scale = part[0][1];
   }
 
-  int linearize(EgRec* out) {
+  int linearize(LmRec* out) {
     memset(&rec, 0, sizeof(rec));
     for (int e = 0; e < w.ne; e++) {
       for (int k = 0; k < EG_STATES; k++) eg_edge_state(w, e, k, w.est);
@@ -763,7 +676,7 @@ struct EgHostBackend {
     return 0;
   }
 
-  int trial(double lambda, EgRec* out) {
+  int trial(double lambda, LmRec* out) {
     memset(&rec, 0, sizeof(rec));
     const int n = 7 * w.ns;
     L = H;
@@ -781,8 +694,8 @@ struct EgHostBackend {
           w.L[eg_at(w, i, j)] = v / w.d[j];
         } else {
           w.d[i] = v;
-          if (!po_finite(v)) eg_fail(w, EG_FLAG_NONFINITE);
-          else if (v == 0.0) eg_fail(w, 0);
+          if (!po_finite(v)) lm_fail(w.rec, LM_FLAG_NONFINITE);
+          else if (v == 0.0) lm_fail(w.rec, 0);
         }
       }
     }

@@ -1,9 +1,9 @@
 // orbfe_lba.hip -- Optimizer::LocalBundleAdjustment on the GPU (include/orbfe_lba.h): one local map's
 // Levenberg-Marquardt with a Schur complement over the free keyframes.
 //
-// The Levenberg control flow (lba_run / lba_optimize of orbfe_lba_core.h) runs on the host and reads one
-// LbaRec per linearisation and per trial; the stages are kernels on the handle's one stream, each a
-// thread- or lane-per-element call of the core header's functions:
+// The Levenberg control flow (lba_run of orbfe_lba_core.h over lm_host_optimize of orbfe_lm_core.h) runs on
+// the host and reads one LmRec per linearisation and per trial; the stages are kernels on the handle's
+// one stream, each a thread- or lane-per-element call of the core header's functions:
 //   k_lba_edge      per active edge: error, robust weight and (linearisation) Jacobians and the edge's
 //                   own Hll, bl, Hpl, Hpp, bp products
 //   k_lba_point     per point: Hll, bl, chi2 share over its edges in order
@@ -27,10 +27,10 @@
 #include "orbfe_ktimer.h"
 #include "orbfe_lba_core.h"
 
-static_assert(LBA_FLAG_LARGE_STEP == ORBFE_LBA_FLAG_LARGE_STEP && LBA_FLAG_NONFINITE == ORBFE_LBA_FLAG_NONFINITE, "flag values");
-static_assert(LBA_STOP_ALL == ORBFE_LBA_STOP_ALL && LBA_STOP_TERMINATE == ORBFE_LBA_STOP_TERMINATE &&
-                  LBA_STOP_NBAD == ORBFE_LBA_STOP_NBAD && LBA_STOP_NO_EDGE == ORBFE_LBA_STOP_NO_EDGE &&
-                  LBA_STOP_FLAG == ORBFE_LBA_STOP_FLAG,
+static_assert(LM_FLAG_LARGE_STEP == ORBFE_LBA_FLAG_LARGE_STEP && LM_FLAG_NONFINITE == ORBFE_LBA_FLAG_NONFINITE, "flag values");
+static_assert(LM_STOP_ALL == ORBFE_LBA_STOP_ALL && LM_STOP_TERMINATE == ORBFE_LBA_STOP_TERMINATE &&
+                  LM_STOP_NBAD == ORBFE_LBA_STOP_NBAD && LM_STOP_NO_EDGE == ORBFE_LBA_STOP_NO_EDGE &&
+                  LM_STOP_FLAG == ORBFE_LBA_STOP_FLAG,
               "stop codes");
 static_assert(sizeof(LbaRound) == sizeof(orbfe_lba_round_t), "trace layout");
 static_assert(LBA_MAX_FREE == ORBFE_LBA_MAX_FREE_KF, "free keyframe cap");
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(LBA_LDLT_THREADS) void k_lba_ldlt(LbaWs w) {
     __syncthreads();
     const double dj = s_d;
     if (!po_finite(dj) || dj == 0.0) {  // the same dj in every thread
-      if (tid == 0) lba_fail(w, po_finite(dj) ? 0u : LBA_FLAG_NONFINITE);
+      if (tid == 0) lm_fail(w.rec, po_finite(dj) ? 0u : LM_FLAG_NONFINITE);
       return;
     }
 #pragma unroll
@@ -180,7 +180,7 @@ struct orbfe_lba {
   hipStream_t stream = nullptr;
   uint8_t* d_pool = nullptr;
   size_t pool_bytes = 0;
-  LbaRec* h_rec = nullptr;  // pinned
+  LmRec* h_rec = nullptr;  // pinned
   LbaWs w;                  // device pointers, sized for the handle's bounds
   uint8_t* d_flag = nullptr;
 };
@@ -233,7 +233,7 @@ static size_t lba_carve(orbfe_lba* h, uint8_t* base) {
   LBA_TAKE(d, double, n);
   LBA_TAKE(y, double, n);
   LBA_TAKE(xp, double, n);
-  LBA_TAKE(rec, LbaRec, 1);
+  LBA_TAKE(rec, LmRec, 1);
 #undef LBA_TAKE
   h->d_flag = take(ne);
   return off;
@@ -274,7 +274,7 @@ extern "C" int orbfe_lba_create(int device, int max_free_kf, int max_kf, int max
   LBA_TRY(hipSetDevice(device));
   LBA_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   LBA_TRY(hipMalloc(&h->d_pool, h->pool_bytes));
-  LBA_TRY(hipHostMalloc(&h->h_rec, sizeof(LbaRec), hipHostMallocDefault));
+  LBA_TRY(hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
 #undef LBA_TRY
   lba_carve(h, h->d_pool);
   *out = h;
@@ -347,16 +347,16 @@ struct LbaDevBackend {
     return ORBFE_OK;
   }
 
-  int read_rec(LbaRec* out) {
+  int read_rec(LmRec* out) {
     ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_rec, w.rec, sizeof(LbaRec), hipMemcpyDeviceToHost, h->stream));
+    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_rec, w.rec, sizeof(LmRec), hipMemcpyDeviceToHost, h->stream));
     ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
     *out = *h->h_rec;
     return ORBFE_OK;
   }
 
-  int linearize(LbaRec* out) {
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LbaRec), h->stream));
+  int linearize(LmRec* out) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LmRec), h->stream));
     ORBFE_LAUNCH("k_lba_edge", k_lba_edge<true>, dim3(lba_grid(w.ne)), dim3(LBA_BLOCK), 0, h->stream, w, 0);
     ORBFE_LAUNCH("k_lba_point", k_lba_point<true>, dim3(lba_grid(w.np)), dim3(LBA_BLOCK), 0, h->stream, w);
     if (w.nslot > 0) ORBFE_LAUNCH("k_lba_pose", k_lba_pose, dim3(w.nslot), dim3(LBA_LANES), 0, h->stream, w);
@@ -364,8 +364,8 @@ struct LbaDevBackend {
     return read_rec(out);
   }
 
-  int trial(double lambda, LbaRec* out) {
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LbaRec), h->stream));
+  int trial(double lambda, LmRec* out) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LmRec), h->stream));
     ORBFE_LAUNCH("k_lba_dinv", k_lba_dinv, dim3(lba_grid(w.np)), dim3(LBA_BLOCK), 0, h->stream, w, lambda);
     if (w.nslot > 0)
       ORBFE_LAUNCH("k_lba_schur", k_lba_schur, dim3(w.nslot, w.nslot), dim3(LBA_LANES), 0, h->stream, w, lambda);

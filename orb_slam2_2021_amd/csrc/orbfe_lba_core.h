@@ -4,10 +4,12 @@
 // OptimizationAlgorithmLevenberg, SparseOptimizer's optimize / push / pop / update) as host/device
 // inline functions over one workspace of plain arrays (LbaWs). The kernels of orbfe_lba.hip call the
 // per-element functions with one thread, or one wavefront lane, each; LbaHostBackend below loops the same
-// functions on the host; lba_run is the Levenberg control flow, on the host for both. Used by
-// orbfe_lba.hip and tests/cpp/lba_core_main.cpp; tests/lba_ref.py is the same code in Python. Not part
-// of the C ABI. The SE3 rules, po_sincos and the "EIGEN:" readings of orbfe_poseopt_core.h are reused
-// unedited; every operation is an IEEE double + - * / sqrt, rounded separately (-ffp-contract=off).
+// functions on the host; lba_run is the two rounds over orbfe_lm_core.h's Levenberg driver
+// (lm_host_optimize), on the host for both. Used by orbfe_lba.hip and tests/cpp/lba_core_main.cpp;
+// tests/lba_ref.py is the same code in Python. Not part of the C ABI. The SE3 rules, po_sincos and the
+// "EIGEN:" readings of orbfe_poseopt_core.h are reused; the flag and stop codes, the record (LmRec), the
+// host group and po_finite are orbfe_lm_core.h's. Every operation is an IEEE double + - * / sqrt, rounded
+// separately (-ffp-contract=off).
 //
 // Summation (the rule that defines the numbers):
 //   per point   Hll, bl, cl and the point's share of the robust chi2 run over the point's active edges
@@ -19,19 +21,13 @@
 // Every loop is capped by a count the host has checked; every index read from memory was checked by the
 // host (orbfe_lba_solve) or built by it (lba_plan).
 #pragma once
-#include "orbfe_poseopt_core.h"
+#include "orbfe_lm_core.h"
+#include "orbfe_poseopt_core.h"  // SE3: PoSE3, po_se3_*, po_quat_to_matrix
 
 #include <cstring>
 #include <vector>
 
 #define LBA_LANES 64
-#define LBA_FLAG_LARGE_STEP 1u /* == ORBFE_LBA_FLAG_LARGE_STEP */
-#define LBA_FLAG_NONFINITE 2u  /* == ORBFE_LBA_FLAG_NONFINITE */
-#define LBA_STOP_ALL 0
-#define LBA_STOP_TERMINATE 1
-#define LBA_STOP_NBAD 2
-#define LBA_STOP_NO_EDGE 3
-#define LBA_STOP_FLAG 4 /* the stop flag read true at a poll */
 #define LBA_MAX_FREE 128
 #define LBA_EDGE_DOUBLES 58 /* per-edge products: rho0, Hll 9, bl 3, Hpl 18, Hpp 21 (r <= c), bp 6 (e_prod) */
 static_assert(LBA_EDGE_DOUBLES == 1 + 9 + 3 + 18 + 21 + 6, "e_prod layout");
@@ -39,13 +35,6 @@ static_assert(LBA_EDGE_DOUBLES == 1 + 9 + 3 + 18 + 21 + 6, "e_prod layout");
 struct LbaRound {
   int32_t n_active, iterations, trials, rejected_trials, stop, n_flagged;
   double lambda, chi2;
-};
-
-// What the host reads per linearisation (chi, maxdiag) and per trial (chi, scale, fail, flags).
-struct LbaRec {
-  double chi, scale, maxdiag;
-  int32_t fail;
-  uint32_t flags;
 };
 
 struct LbaWs {
@@ -89,28 +78,10 @@ struct LbaWs {
   double* d;    // [n]
   double* y;    // [n]
   double* xp;   // [nfree * 6] by slot
-  LbaRec* rec;
+  LmRec* rec;
 };
 
 PO_HD inline int lba_upper(int r, int c) { return r * 6 - r * (r - 1) / 2 + (c - r); }  // r <= c
-
-PO_HD inline void lba_or(uint32_t* p, uint32_t v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  if (v) atomicOr(p, v);
-#else
-  *p |= v;
-#endif
-}
-
-PO_HD inline void lba_fail(const LbaWs& w, uint32_t flag) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  atomicOr(reinterpret_cast<uint32_t*>(&w.rec->fail), 1u);
-  if (flag) atomicOr(&w.rec->flags, flag);
-#else
-  w.rec->fail = 1;
-  w.rec->flags |= flag;
-#endif
-}
 
 PO_HD inline void lba_load_T(const double* a, PoSE3* T) {
   for (int k = 0; k < 4; k++) T->q[k] = a[k];
@@ -344,7 +315,7 @@ PO_HD inline void lba_point_dinv(const LbaWs& w, int p, double lambda) {
   }
   const double* b = w.p_bl + 3 * (size_t)p;
   for (int r = 0; r < 3; r++) w.p_db[3 * (size_t)p + r] = (inv[3 * r] * b[0] + inv[3 * r + 1] * b[1]) + inv[3 * r + 2] * b[2];
-  if (!ok) lba_fail(w, LBA_FLAG_NONFINITE);  // deviation: a non-finite Dinv fails the trial
+  if (!ok) lm_fail(w.rec, LM_FLAG_NONFINITE);  // deviation: a non-finite Dinv fails the trial
 }
 
 // One lane's part of sum_p (B_f1 Dinv) B_f2^T (36) and, on the diagonal, of sum_p B_f db (6): the points
@@ -403,7 +374,7 @@ PO_HD inline void lba_schur_finish(const LbaWs& w, int s1, int s2, double lambda
       w.bs[6 * s1 + r] = v;
       ok = ok && po_finite(v);
     }
-  if (!ok) lba_fail(w, LBA_FLAG_NONFINITE);
+  if (!ok) lm_fail(w.rec, LM_FLAG_NONFINITE);
 }
 
 // Deviation: the dense, unpivoted LDL^T in natural order that stands for LinearSolverEigen's sparse
@@ -459,7 +430,7 @@ PO_HD inline void lba_update_kf(const LbaWs& w, int kf) {
   po_se3_exp(w.xp + 6 * s, &d, &flags);
   po_se3_mul(d, T, &o);
   lba_store_T(o, w.tri_T + 7 * (size_t)kf);
-  lba_or(&w.rec->flags, flags);
+  lm_or(&w.rec->flags, flags);
 }
 
 // One lane's part of the sums over points: out[0] the robust chi2, out[1] computeScale's point partials
@@ -631,76 +602,21 @@ struct LbaPoller {
   }
 };
 
-// SparseOptimizer::optimize(max_it) with OptimizationAlgorithmLevenberg::solve. A backend B supplies
-// begin_round, linearize, trial, accept; each returns 0 or an error status that ends the run.
+// One round: SparseOptimizer::optimize(max_it) by orbfe_lm_core.h's lm_host_optimize, lambda from the
+// diagonal. A backend B supplies begin_round, linearize, trial, accept; each returns 0 or an error status
+// that ends the run.
 template <class B>
-inline int lba_optimize(B& b, const LbaActive& A, bool kernel_on, int max_it, LbaPoller& poll, LbaRound* tr, uint32_t* flags) {
-  LbaRound r = {A.n_edges, 0, 0, 0, LBA_STOP_ALL, 0, 0.0, 0.0};
-  int st = 0;
-  if (A.n_edges == 0) {
-    r.stop = LBA_STOP_NO_EDGE;  // _ivMap.size() == 0: optimize() returns -1 without a step
-    *tr = r;
-    return 0;
+inline int lba_round(B& b, const LbaActive& A, bool kernel_on, int max_it, LbaPoller& poll, LbaRound* tr, uint32_t* flags) {
+  LbaRound r = {A.n_edges, 0, 0, 0, LM_STOP_NO_EDGE, 0, 0.0, 0.0};
+  if (A.n_edges > 0) {  // else _ivMap.size() == 0: optimize() returns -1 without a step
+    int st = 0;
+    LmTrace t;
+    if ((st = b.begin_round(A, kernel_on))) return st;
+    if ((st = lm_host_optimize(b, max_it, 0.0, poll, &t))) return st;
+    r.iterations = t.iterations, r.trials = t.trials, r.rejected_trials = t.rejected_trials, r.stop = t.stop;
+    r.lambda = t.lambda, r.chi2 = t.chi2;
+    *flags |= t.flags;
   }
-  if ((st = b.begin_round(A, kernel_on))) return st;
-  double lambda = 0.0, current = 0.0, ni = 2.0;
-  int nbad = 0;
-  for (int i = 0; i < max_it; i++) {
-    if (poll()) {
-      r.stop = LBA_STOP_FLAG;
-      break;
-    }
-    r.iterations++;
-    LbaRec rec;
-    if ((st = b.linearize(&rec))) return st;
-    const double ini = rec.chi;
-    current = ini;
-    if (i == 0) {
-      lambda = 1e-5 * rec.maxdiag;
-      ni = 2.0;
-      nbad = 0;
-    }
-    double rho = 0.0;
-    int qmax = 0;
-    bool more;
-    do {
-      if ((st = b.trial(lambda, &rec))) return st;
-      *flags |= rec.flags;
-      double temp = rec.chi;
-      if (rec.fail) temp = DBL_MAX;  // ok2 == false
-      rho = current - temp;
-      rho = rho / (rec.scale + 1e-3);
-      r.trials++;
-      if (rho > 0 && po_finite(temp)) {
-        const double y = 2 * rho - 1;
-        double alpha = 1.0 - y * y * y;  // deviation: pow(2 * rho - 1, 3) as x * x * x
-        alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;
-        const double factor = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;
-        lambda = lambda * factor;
-        ni = 2.0;
-        current = temp;
-        if ((st = b.accept())) return st;  // discardTop
-      } else {
-        lambda = lambda * ni;
-        ni = ni * 2;
-        r.rejected_trials++;  // pop: the accepted estimates stand
-      }
-      qmax++;
-      more = rho < 0 && qmax < 10;
-      if (more && poll()) more = false;  // ... && !terminate(), polled only when reached
-    } while (more);
-    if (qmax == 10 || rho == 0) {
-      r.stop = LBA_STOP_TERMINATE;
-      break;
-    }
-    if ((ini - current) * 1e3 < ini) nbad++;
-    else nbad = 0;
-    if (nbad >= 3) {
-      r.stop = LBA_STOP_NBAD;
-      break;
-    }
-  }
-  r.lambda = lambda, r.chi2 = current;
   *tr = r;
   return 0;
 }
@@ -721,7 +637,7 @@ inline int lba_run(B& b, const LbaIn& in, const LbaPlan& P, LbaOut* o) {
     LbaActive A;
     lba_active(in, P, nullptr, &A);
     if ((st = b.start(P))) return st;
-    if ((st = lba_optimize(b, A, true, 5, poll, &o->rounds[0], &o->flags))) return st;
+    if ((st = lba_round(b, A, true, 5, poll, &o->rounds[0], &o->flags))) return st;
     o->rounds_run = 1;
     if (!poll()) {  // :667
       if ((st = b.classify(o->level1.data()))) return st;
@@ -729,7 +645,7 @@ inline int lba_run(B& b, const LbaIn& in, const LbaPlan& P, LbaOut* o) {
       for (int e = 0; e < in.ne; e++) n1 += o->level1[e];
       o->rounds[0].n_flagged = n1;
       lba_active(in, P, o->level1.data(), &A);
-      if ((st = lba_optimize(b, A, false, 10, poll, &o->rounds[1], &o->flags))) return st;
+      if ((st = lba_round(b, A, false, 10, poll, &o->rounds[1], &o->flags))) return st;
       o->rounds_run = 2;
     }
     if ((st = b.classify(o->erase.data()))) return st;
@@ -755,7 +671,7 @@ inline int lba_run(B& b, const LbaIn& in, const LbaPlan& P, LbaOut* o) {
 // The workspace in host memory, every stage a loop over the per-element functions
 struct LbaHostBackend {
   LbaWs w;
-  LbaRec rec;
+  LmRec rec;
   const LbaPlan* P = nullptr;
   LbaActive A;
   std::vector<double> est_T, tri_T, est_X, tri_X, e_err, e_prod, p_hll, p_bl, p_chi, p_dinv, p_db, p_xl, hpp, bp, S, bs, Lm, Mm,
@@ -817,14 +733,14 @@ struct LbaHostBackend {
     lba_reduce_finish(w, mode, lambda, part[0][0], part[0][1]);
   }
 
-  int linearize(LbaRec* out) {
+  int linearize(LmRec* out) {
     memset(&rec, 0, sizeof(rec));
     tree_reduce(0, 0.0, false);
     *out = rec;
     return 0;
   }
 
-  int trial(double lambda, LbaRec* out) {
+  int trial(double lambda, LmRec* out) {
     memset(&rec, 0, sizeof(rec));
     const int n = 6 * w.nslot;
     for (int p = 0; p < w.np; p++) lba_point_dinv(w, p, lambda);
@@ -840,8 +756,8 @@ struct LbaHostBackend {
     for (int j = 0; j < n && !rec.fail; j++) {
       const double dj = lba_ldlt_dot(w, n, j, j);
       w.d[j] = dj;
-      if (!po_finite(dj)) lba_fail(w, LBA_FLAG_NONFINITE);
-      else if (dj == 0.0) lba_fail(w, 0);
+      if (!po_finite(dj)) lm_fail(w.rec, LM_FLAG_NONFINITE);
+      else if (dj == 0.0) lm_fail(w.rec, 0);
       if (rec.fail) break;
       for (int i = j + 1; i < n; i++) {
         const double l = lba_ldlt_dot(w, n, i, j) / dj;

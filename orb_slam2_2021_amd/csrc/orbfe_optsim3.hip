@@ -15,7 +15,7 @@
 // (max_obs <= 64 * 64) and the stale errors are recomputed from the last evaluated estimate, so the
 // kernel needs no per-edge workspace.
 //
-// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): 256 VGPRs, 106 SGPRs (29 spilled to vector
+// Resources (-Rpass-analysis=kernel-resource-usage, gfx950): 256 VGPRs, 106 SGPRs (36 spilled to vector
 // lanes), 0 bytes of scratch, no VGPR spill, 10,448 bytes of LDS per block. An edge's Jacobian goes through
 // the lane's column of OsWork::J in LDS with the loop over the 7 dimensions kept rolled; unrolled, the
 // table's loads were hoisted out of the correspondence loop and the kernel spilled.
@@ -27,6 +27,7 @@
 #include "../../include/orbfe_optsim3.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_lm_device.h"
 #include "orbfe_optsim3_core.h"
 
 static_assert(ORBFE_OPTSIM3_MAX_OBS <= PO_LANES * 64, "a lane's removal flags are one 64-bit word");
@@ -43,36 +44,11 @@ struct OsDev {
   unsigned long long in_valid, in_p1, in_p2, in_kp1, in_kp2, in_is1, in_is2, o_out, o_mask;
 };
 
-struct OsDevGroup {
-  static constexpr int width = PO_LANES;
-  static constexpr int slots = 1;
-  __device__ int lane() const { return threadIdx.x; }
-  __device__ void sync() const { __syncthreads(); }  // the block is one wavefront
-  double* red;  // LDS, OS_ACC doubles
-  // The tree of orbfe_poseopt.hip: after the step of `stride` lanes 0 .. stride-1 hold s[l] + s[l + stride];
-  // lane 0's sums go to every lane through LDS, which keeps them in vector registers.
-  template <int N>
-  __device__ void reduce(double (*s)[N]) const {
-    __syncthreads();  // every lane has read the previous sums
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-      double v = s[0][k];
-#pragma unroll
-      for (int stride = PO_LANES / 2; stride >= 1; stride >>= 1) v = v + __shfl_down(v, stride);
-      if (threadIdx.x == 0) red[k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) s[0][k] = red[k];
-  }
-  __device__ uint64_t ballot(const uint64_t* bits, int c) const { return __ballot((int)((bits[0] >> c) & 1ull)); }
-};
-
 __global__ __launch_bounds__(PO_LANES) void k_optsim3(const uint8_t* __restrict__ in, uint8_t* __restrict__ res) {
   const OsDev& D = reinterpret_cast<const OsDev*>(in)[blockIdx.x];
   __shared__ OsWork work;
   __shared__ double red[OS_ACC];
-  // the cameras and the start go through LDS for the same reason as the sums (OsDevGroup::reduce)
+  // the cameras and the start go through LDS for the same reason as the sums (LmDevGroup::reduce)
   __shared__ double cam[9];
   __shared__ float start[13];
   __shared__ float kf2[12];
@@ -97,7 +73,7 @@ __global__ __launch_bounds__(PO_LANES) void k_optsim3(const uint8_t* __restrict_
   P.th2 = cam[8];
   P.start = start;
   P.kf2 = kf2;
-  OsDevGroup g;
+  LmDevGroup g;
   g.red = red;
   os_optimize(g, P, work, reinterpret_cast<OsOut*>(res + D.o_out), reinterpret_cast<uint64_t*>(res + D.o_mask));
 }

@@ -7,11 +7,12 @@
 //
 // Every operation is an IEEE double (or float) + - * / sqrt, rounded separately (-ffp-contract=off).
 // No libm call: sin / cos are orbfe_poseopt_core.h's po_sincos, std::exp of Sim3(update) is restated
-// below (os_exp), pow(x, 3) is x * x * x. Every Eigen operation is restated by the rule DESIGN.md
+// below (os_exp), pow(x, 3) is a product. Every Eigen operation is restated by the rule DESIGN.md
 // sections 18 and 19 record, marked "EIGEN:"; tests/optsim3_ref.py is the same code in Python, line by
 // line.
 //
-// A problem is run by a group of PO_LANES lanes (orbfe_poseopt_core.h's group abstraction).
+// A problem is run by a group of PO_LANES lanes (orbfe_lm_core.h's group abstraction); the Levenberg
+// controller (LmCtl) and the 7x7 LDLT (lm_ldlt<7>) are that header's too.
 // Correspondence i (KF1's keypoint index) belongs to lane i % PO_LANES; a lane adds, in ascending i,
 // first e12 then e21 of its active correspondences into OS_ACC accumulators that start at +0.0, and the
 // lanes are combined by s[l] += s[l + stride], stride = 32 .. 1. The Jacobians are numeric, as in the
@@ -24,8 +25,8 @@
 //    small fixed-size products taken in plain left-to-right scalar order; the information matrix is
 //    read as the diagonal it is (no 0 * e terms);
 //  - exp, sin, cos from + - * / (os_exp within 1 ulp of libm on [-1, 1], po_sincos as section 18);
-//    pow(2 rho - 1, 3) is x * x * x. A rotation step above pi sets PO_FLAG_LARGE_STEP;
-//  - PO_FLAG_NONFINITE: a non-finite entry of H + lambda I or b makes the trial fail as a non-positive
+//    pow(2 rho - 1, 3) is a product (orbfe_lm_core.h). A rotation step above pi sets LM_FLAG_LARGE_STEP;
+//  - LM_FLAG_NONFINITE: a non-finite entry of H + lambda I or b makes the trial fail as a non-positive
 //    factorisation does (tempChi = DBL_MAX, rejected); Eigen's pivot search is not followed over NaN;
 //  - the increment x is zero before a round's first successful solve; g2o leaves it as allocated.
 //
@@ -33,7 +34,8 @@
 // uniform; every loop has a fixed cap (2 rounds, 10 iterations, 10 trials, 7 pivots, ceil(n / 64) <= 64
 // correspondences per lane) and no computed value forms an address.
 #pragma once
-#include "orbfe_poseopt_core.h"
+#include "orbfe_lm_core.h"
+#include "orbfe_poseopt_core.h"  // po_sincos and the quaternion rules
 
 #define OS_ACC 36     // 28 lower entries of H (row-major over r >= c), 7 of b, the robust chi2
 #define OS_STATES 15  // the estimate, then oplus(+delta e_d), oplus(-delta e_d) for d = 0 .. 6
@@ -385,78 +387,6 @@ PO_HD inline void os_sums_chi(const G& g, const OsProblem& P, const uint64_t* re
   g.reduce(s);
 }
 
-// ---- the 7x7 solve (one lane) ----------------------------------------------------------------------
-// EIGEN: LDLT<MatrixXd, Lower>::compute, unblocked and in place on the lower triangle of w.A (row r,
-// column c at A[7 r + c], only r >= c touched), by section 18's rules with n = 7.
-PO_HD inline bool os_ldlt(OsWork& w) {
-  const int n = 7;
-  double* A = w.A;
-  int sign = 0;  // ZeroSign; 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
-  for (int k = 0; k < n; k++) w.tr[k] = k;
-  for (int k = 0; k < n; k++) {
-    int big = k;
-    double best = fabs(A[8 * k]);
-    for (int j = k + 1; j < n; j++)
-      if (fabs(A[8 * j]) > best) big = j, best = fabs(A[8 * j]);
-    w.tr[k] = big;
-    if (k != big) {
-      const int p = big;  // k < p < 7
-      double tmp;
-      for (int j = 0; j < k; j++) tmp = A[7 * k + j], A[7 * k + j] = A[7 * p + j], A[7 * p + j] = tmp;
-      for (int i = p + 1; i < n; i++) tmp = A[7 * i + k], A[7 * i + k] = A[7 * i + p], A[7 * i + p] = tmp;
-      tmp = A[8 * k], A[8 * k] = A[8 * p], A[8 * p] = tmp;
-      for (int i = k + 1; i < p; i++) tmp = A[7 * i + k], A[7 * i + k] = A[7 * p + i], A[7 * p + i] = tmp;
-    }
-    if (k > 0) {
-      for (int j = 0; j < k; j++) w.temp[j] = A[8 * j] * A[7 * k + j];
-      double s = A[7 * k] * w.temp[0];
-      for (int j = 1; j < k; j++) s = s + A[7 * k + j] * w.temp[j];
-      A[8 * k] = A[8 * k] - s;
-      for (int i = k + 1; i < n; i++) {
-        s = A[7 * i] * w.temp[0];
-        for (int j = 1; j < k; j++) s = s + A[7 * i + j] * w.temp[j];
-        A[7 * i + k] = A[7 * i + k] - s;
-      }
-    }
-    const double akk = A[8 * k];
-    const bool valid = fabs(akk) > 0.0;
-    if (k == 0 && !valid) {  // the whole diagonal is zero: ZeroSign, isPositive()
-      for (int j = 0; j < n; j++) w.tr[j] = j;
-      return true;
-    }
-    if (valid)
-      for (int i = k + 1; i < n; i++) A[7 * i + k] = A[7 * i + k] / akk;
-    if (sign == 1) {
-      if (akk < 0) sign = 2;
-    } else if (sign == -1) {
-      if (akk > 0) sign = 2;
-    } else if (sign == 0) {
-      if (akk > 0) sign = 1;
-      else if (akk < 0) sign = -1;
-    }
-  }
-  return sign == 1 || sign == 0;
-}
-
-// EIGEN: LDLT::solve on w.rhs into w.x, as section 18 with n = 7. tr[k] is in k..6.
-PO_HD inline void os_ldlt_solve(OsWork& w) {
-  const int n = 7;
-  const double* A = w.A;
-  double* x = w.rhs;
-  double tmp;
-  for (int k = 0; k < n; k++) tmp = x[k], x[k] = x[w.tr[k]], x[w.tr[k]] = tmp;
-  for (int i = 0; i < n; i++)
-    for (int r = i + 1; r < n; r++) x[r] = x[r] - x[i] * A[7 * r + i];
-  for (int i = 0; i < n; i++) x[i] = fabs(A[8 * i]) > DBL_MIN ? x[i] / A[8 * i] : 0.0;
-  for (int i = n - 2; i >= 0; i--) {
-    double s = A[7 * (i + 1) + i] * x[i + 1];
-    for (int j = i + 2; j < n; j++) s = s + A[7 * j + i] * x[j];
-    x[i] = x[i] - s;
-  }
-  for (int k = n - 1; k >= 0; k--) tmp = x[k], x[k] = x[w.tr[k]], x[w.tr[k]] = tmp;
-  for (int i = 0; i < n; i++) w.x[i] = x[i];
-}
-
 // ---- OptimizeSim3 ----------------------------------------------------------------------------------
 // mask: ceil(n / 64) words, bit i % 64 of word i / 64 = "vpMatches1[i] was set to NULL". Lane 0 writes o
 // and mask.
@@ -494,17 +424,15 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
     if (it == 1 && n_corr - n_bad < 10) break;  // :1220: return 0, g2oS12 untouched
     const int max_iter = it == 0 ? 5 : (n_bad > 0 ? 10 : 5);
     const int n_active = n_corr - n_bad;
-    int iterations = 0, trials = 0, rejected = 0, stop = PO_STOP_ALL;
-    double lambda = 0.0, current = 0.0;
+    int iterations = 0, trials = 0, rejected = 0, stop = LM_STOP_ALL;
+    LmCtl lm = {0.0, 0.0, 0.0, 2.0, 0.0, 0, 0};
     if (n_active == 0) {
-      stop = PO_STOP_NO_EDGE;
+      stop = LM_STOP_NO_EDGE;
     } else {
       g.sync();
       if (lane == 0)
         for (int j = 0; j < 7; j++) w.x[j] = 0.0;  // deviation: zero before a round's first successful solve
       g.sync();
-      double ni = 2.0;
-      int nbad_steps = 0;
       for (int i = 0; i < 10; i++) {
         if (i >= max_iter) break;
         iterations++;
@@ -517,8 +445,7 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
           g.sync();
         }
         const double* s = w.S;  // read where needed: 36 doubles are not held across the trials
-        const double ini = s[35];
-        current = ini;
+        double lambda_init = 0.0;
         if (i == 0) {
           double mx = 0.0;
 #pragma unroll
@@ -526,13 +453,11 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
             const double a = fabs(s[j * (j + 1) / 2 + j]);
             mx = a < mx ? mx : a;  // std::max(fabs(H_jj), maxDiagonal)
           }
-          lambda = 1e-5 * mx;
-          ni = 2.0;
-          nbad_steps = 0;
+          lambda_init = 1e-5 * mx;
         }
-        double rho = 0.0;
-        int qmax = 0;
+        lm_begin_iteration(lm, s[35], i == 0, lambda_init);
         do {
+          const double lambda = lm.lambda;
           // setLambda + LinearSolverDense::solve. Deviation: a non-finite entry gives ok2 = false
           bool ok2 = true;
 #pragma unroll
@@ -540,7 +465,7 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
           ok2 = ok2 && po_finite(lambda);
 #pragma unroll
           for (int j = 0; j < 7; j++) ok2 = ok2 && po_finite(s[j * (j + 1) / 2 + j] + lambda);
-          if (!ok2) flags |= PO_FLAG_NONFINITE;
+          if (!ok2) flags |= LM_FLAG_NONFINITE;
           g.sync();
           if (lane == 0 && ok2) {
 #pragma unroll
@@ -549,8 +474,8 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
               for (int c = 0; c <= r; c++) w.A[7 * r + c] = r == c ? s[r * (r + 1) / 2 + c] + lambda : s[r * (r + 1) / 2 + c];
               w.rhs[r] = s[28 + r];
             }
-            w.positive = os_ldlt(w) ? 1 : 0;
-            if (w.positive) os_ldlt_solve(w);
+            w.positive = lm_ldlt<7>(w.A, w.tr, w.temp) ? 1 : 0;
+            if (w.positive) lm_ldlt_solve<7>(w.A, w.tr, w.rhs, w.x);
           }
           g.sync();
           ok2 = ok2 && w.positive != 0;
@@ -566,41 +491,15 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
           os_store_state(Ti, trial_inv);
           double C[G::slots][1];
           os_sums_chi(g, P, rem, T, Ti, delta, dsqr, C);
-          double temp = C[0][0];
-          if (!ok2) temp = DBL_MAX;
-          rho = current - temp;
           double scale = 0.0;
 #pragma unroll
           for (int j = 0; j < 7; j++) scale = scale + x[j] * (lambda * x[j] + s[28 + j]);
-          scale = scale + 1e-3;
-          rho = rho / scale;
           trials++;
-          if (rho > 0 && po_finite(temp)) {
-            const double y = 2 * rho - 1;
-            double alpha = 1.0 - y * y * y;  // deviation: pow(2 * rho - 1, 3) as x * x * x
-            alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;
-            const double factor = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;
-            lambda = lambda * factor;
-            ni = 2.0;
-            current = temp;
-            est = trial;
-          } else {
-            lambda = lambda * ni;
-            ni = ni * 2;
-            rejected++;
-          }
-          qmax++;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) {
-          stop = PO_STOP_TERMINATE;
-          break;
-        }
-        if ((ini - current) * 1e3 < ini) nbad_steps++;
-        else nbad_steps = 0;
-        if (nbad_steps >= 3) {
-          stop = PO_STOP_NBAD;
-          break;
-        }
+          if (lm_trial(lm, C[0][0], !ok2, scale)) est = trial;
+          else rejected++;
+        } while (lm_more_trials(lm));
+        stop = lm_end_iteration(lm);
+        if (stop != LM_STOP_ALL) break;
       }
     }
     // :1195-1212, :1229-1243: an active correspondence is removed when e12->chi2() > th2 ||
@@ -631,7 +530,7 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
     for (int c = 0; c < words; c++) n_bad += (int)__builtin_popcountll(g.ballot(rem, c));
     rounds_run = it + 1;
     if (lane == 0) {
-      PoRound r = {n_active, iterations, trials, rejected, stop, n_bad, lambda, current};
+      PoRound r = {n_active, iterations, trials, rejected, stop, n_bad, lm.lambda, lm.current};
       o->rounds[it] = r;
     }
   }

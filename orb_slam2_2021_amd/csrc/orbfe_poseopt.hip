@@ -19,12 +19,13 @@
 #include "../../include/orbfe_poseopt.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_lm_device.h"
 #include "orbfe_poseopt_core.h"
 
-static_assert(PO_FLAG_LARGE_STEP == ORBFE_POSEOPT_FLAG_LARGE_STEP && PO_FLAG_NONFINITE == ORBFE_POSEOPT_FLAG_NONFINITE,
+static_assert(LM_FLAG_LARGE_STEP == ORBFE_POSEOPT_FLAG_LARGE_STEP && LM_FLAG_NONFINITE == ORBFE_POSEOPT_FLAG_NONFINITE,
               "flag values");
-static_assert(PO_STOP_ALL == ORBFE_POSEOPT_STOP_ALL && PO_STOP_TERMINATE == ORBFE_POSEOPT_STOP_TERMINATE &&
-                  PO_STOP_NBAD == ORBFE_POSEOPT_STOP_NBAD && PO_STOP_NO_EDGE == ORBFE_POSEOPT_STOP_NO_EDGE,
+static_assert(LM_STOP_ALL == ORBFE_POSEOPT_STOP_ALL && LM_STOP_TERMINATE == ORBFE_POSEOPT_STOP_TERMINATE &&
+                  LM_STOP_NBAD == ORBFE_POSEOPT_STOP_NBAD && LM_STOP_NO_EDGE == ORBFE_POSEOPT_STOP_NO_EDGE,
               "stop codes");
 static_assert(ORBFE_POSEOPT_MAX_OBS <= PO_LANES * 64, "a lane's outlier flags are one 64-bit word");
 static_assert(sizeof(PoRound) == sizeof(orbfe_poseopt_round_t), "trace layout");
@@ -38,32 +39,6 @@ struct PoDev {
   unsigned long long in_valid, in_xw, in_kp, in_ur, in_is2, o_out, o_mask;
 };
 
-struct PoDevGroup {
-  static constexpr int width = PO_LANES;
-  static constexpr int slots = 1;
-  __device__ int lane() const { return threadIdx.x; }
-  __device__ void sync() const { __syncthreads(); }  // the block is one wavefront
-  double* red;  // LDS, PO_ACC doubles
-  // The tree: after the step of `stride` lanes 0 .. stride-1 hold s[l] + s[l + stride]. Lane 0's sums go
-  // to every lane through LDS, which keeps them in vector registers: as wave-uniform values the
-  // Levenberg state would not fit the scalar register file.
-  template <int N>
-  __device__ void reduce(double (*s)[N]) const {
-    __syncthreads();  // every lane has read the previous sums
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-      double v = s[0][k];
-#pragma unroll
-      for (int stride = PO_LANES / 2; stride >= 1; stride >>= 1) v = v + __shfl_down(v, stride);
-      if (threadIdx.x == 0) red[k] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; k++) s[0][k] = red[k];
-  }
-  __device__ uint64_t ballot(const uint64_t* bits, int c) const { return __ballot((int)((bits[0] >> c) & 1ull)); }
-};
-
 __global__ __launch_bounds__(PO_LANES) void k_poseopt(const uint8_t* __restrict__ in, uint8_t* __restrict__ res) {
   const PoDev& D = reinterpret_cast<const PoDev*>(in)[blockIdx.x];
   __shared__ PoWork work;
@@ -75,7 +50,7 @@ __global__ __launch_bounds__(PO_LANES) void k_poseopt(const uint8_t* __restrict_
   P.kp = reinterpret_cast<const float*>(in + D.in_kp);
   P.ur = reinterpret_cast<const float*>(in + D.in_ur);
   P.inv_sigma2 = reinterpret_cast<const float*>(in + D.in_is2);
-  // the camera and the start pose go through LDS for the same reason as the sums (PoDevGroup::reduce)
+  // the camera and the start pose go through LDS for the same reason as the sums (LmDevGroup::reduce)
   __shared__ double cam[5];
   __shared__ float tcw[12];
   if (threadIdx.x < 5) cam[threadIdx.x] = D.cam[threadIdx.x];
@@ -84,7 +59,7 @@ __global__ __launch_bounds__(PO_LANES) void k_poseopt(const uint8_t* __restrict_
   __syncthreads();
   P.fx = cam[0], P.fy = cam[1], P.cx = cam[2], P.cy = cam[3], P.bf = cam[4];
   P.tcw = tcw;
-  PoDevGroup g;
+  LmDevGroup g;
   g.red = red;
   po_optimize(g, P, work, reinterpret_cast<PoOut*>(res + D.o_out),
               reinterpret_cast<uint64_t*>(res + D.o_mask));

@@ -1,12 +1,13 @@
 // orbfe_poseopt_core.h -- Optimizer::PoseOptimization's arithmetic (Optimizer.cc:242-452 and the g2o
-// routines under it: SE3Quat, the two *OnlyPose edges, RobustKernelHuber, OptimizationAlgorithmLevenberg,
-// BlockSolver's non-Schur path, LinearSolverDense) as host/device inline functions. Used by k_poseopt in
+// routines under it: SE3Quat, the two *OnlyPose edges, RobustKernelHuber, BlockSolver's non-Schur path)
+// as host/device inline functions. OptimizationAlgorithmLevenberg's decisions (LmCtl), LinearSolverDense's
+// LDLT (lm_ldlt<6>), the lane group and the flag and stop codes are orbfe_lm_core.h's. Used by k_poseopt in
 // orbfe_poseopt.hip and by the stand-alone host program tests/cpp/poseopt_core_main.cpp. Not part of
 // the C ABI.
 //
 // Every operation is an IEEE double (or float) + - * / sqrt, rounded separately (-ffp-contract=off).
 // No libm transcendental: sin / cos of SE3Quat::exp are restated below (po_sincos), pow(x, 3) is
-// x * x * x. Every Eigen operation is restated by the rule DESIGN.md section 18 records, marked
+// a product (orbfe_lm_core.h). Every Eigen operation is restated by the rule DESIGN.md section 18 records, marked
 // "EIGEN:"; tests/poseopt_ref.py is the same code in Python, line by line.
 //
 // A problem is run by a group of PO_LANES lanes. Edge i (the frame's keypoint index) belongs to lane
@@ -17,25 +18,9 @@
 // so control flow is uniform; every loop has a fixed cap (4 rounds, 10 iterations, 10 trials, 6 pivots,
 // ceil(n / 64) edges per lane) and no computed value forms an address.
 #pragma once
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define PO_HD __host__ __device__
-#else
-#define PO_HD
-#endif
-#include <stdint.h>
+#include "orbfe_lm_core.h"
 
-#include <cfloat>
-#include <cmath>
-
-#define PO_LANES 64
 #define PO_ACC 28  // 21 lower entries of H (row-major over r >= c), 6 of b, the robust chi2
-#define PO_FLAG_LARGE_STEP 1u  /* == ORBFE_POSEOPT_FLAG_LARGE_STEP */
-#define PO_FLAG_NONFINITE 2u   /* == ORBFE_POSEOPT_FLAG_NONFINITE */
-#define PO_STOP_ALL 0
-#define PO_STOP_TERMINATE 1
-#define PO_STOP_NBAD 2
-#define PO_STOP_NO_EDGE 3
 
 struct PoSE3 {
   double q[4];  // x y z w
@@ -59,11 +44,6 @@ struct PoEdge {
   bool stereo;
 };
 
-struct PoRound {
-  int32_t n_active, iterations, trials, rejected_trials, stop, n_bad;
-  double lambda, chi2;
-};
-
 struct PoOut {
   float tcw[12];
   double pose[7];
@@ -77,26 +57,6 @@ struct PoWork {
   double A[36], x[6], rhs[6], temp[6];
   int tr[6];
   int positive;
-};
-
-struct PoHostGroup {
-  static constexpr int width = 1;
-  static constexpr int slots = PO_LANES;
-  PO_HD int lane() const { return 0; }
-  PO_HD void sync() const {}
-  // s: slots rows of N; the combined sums end in row 0
-  template <int N>
-  PO_HD void reduce(double (*s)[N]) const {
-    for (int stride = PO_LANES / 2; stride >= 1; stride >>= 1)
-      for (int l = 0; l < stride; l++)
-        for (int k = 0; k < N; k++) s[l][k] = s[l][k] + s[l + stride][k];
-  }
-  // bit l of the result: bit c of lane l's word
-  PO_HD uint64_t ballot(const uint64_t* bits, int c) const {
-    uint64_t w = 0;
-    for (int l = 0; l < PO_LANES; l++) w |= ((bits[l] >> c) & 1ull) << l;
-    return w;
-  }
 };
 
 // ---- sin / cos from + - * / ------------------------------------------------------------------------
@@ -125,7 +85,7 @@ PO_HD inline double po_kernel_cos(double x, double y) {
 
 // Deviation: replaces libm's sin / cos. Cody-Waite reduction by pi/2 with the constant split in pieces
 // of 33 bits (k * piece is exact for a small k; each subtraction's rounding error is carried into a
-// tail), then the kernels by quadrant. Defined for every finite theta: above pi it sets PO_FLAG_LARGE_STEP,
+// tail), then the kernels by quadrant. Defined for every finite theta: above pi it sets LM_FLAG_LARGE_STEP,
 // from 2^31 on it returns (0, 1). A non-finite theta gives NaN.
 PO_HD inline void po_sincos(double theta, double* sn, double* cs, unsigned* flags) {
   const double nan = theta - theta;  // 0, or NaN for a non-finite theta
@@ -133,7 +93,7 @@ PO_HD inline void po_sincos(double theta, double* sn, double* cs, unsigned* flag
     *sn = *cs = nan;
     return;
   }
-  if (theta > 3.141592653589793) *flags |= PO_FLAG_LARGE_STEP;
+  if (theta > 3.141592653589793) *flags |= LM_FLAG_LARGE_STEP;
   if (!(theta < 2147483648.0 && theta > -2147483648.0)) {
     *sn = 0.0;
     *cs = 1.0;
@@ -424,82 +384,6 @@ PO_HD inline void po_sums(const G& g, const PoProblem& P, const uint64_t* out, c
   g.reduce(s);
 }
 
-// ---- the 6x6 solve (one lane) ----------------------------------------------------------------------
-// EIGEN: LDLT<MatrixXd, Lower>::compute, unblocked and in place on the lower triangle of w.A (row r,
-// column c at A[6 r + c], only r >= c touched). Pivot: the largest |diagonal| of the trailing part, the
-// first maximum wins; symmetric transpositions; the sign tracked for isPositive().
-PO_HD inline bool po_ldlt(PoWork& w) {
-  const int n = 6;
-  double* A = w.A;
-  int sign = 0;  // ZeroSign; 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
-  for (int k = 0; k < n; k++) w.tr[k] = k;
-  for (int k = 0; k < n; k++) {
-    int big = k;
-    double best = fabs(A[7 * k]);
-    for (int j = k + 1; j < n; j++)
-      if (fabs(A[7 * j]) > best) big = j, best = fabs(A[7 * j]);
-    w.tr[k] = big;
-    if (k != big) {
-      const int p = big;  // k < p < 6
-      double tmp;
-      for (int j = 0; j < k; j++) tmp = A[6 * k + j], A[6 * k + j] = A[6 * p + j], A[6 * p + j] = tmp;
-      for (int i = p + 1; i < n; i++) tmp = A[6 * i + k], A[6 * i + k] = A[6 * i + p], A[6 * i + p] = tmp;
-      tmp = A[7 * k], A[7 * k] = A[7 * p], A[7 * p] = tmp;
-      for (int i = k + 1; i < p; i++) tmp = A[6 * i + k], A[6 * i + k] = A[6 * p + i], A[6 * p + i] = tmp;
-    }
-    if (k > 0) {
-      for (int j = 0; j < k; j++) w.temp[j] = A[7 * j] * A[6 * k + j];
-      double s = A[6 * k] * w.temp[0];
-      for (int j = 1; j < k; j++) s = s + A[6 * k + j] * w.temp[j];
-      A[7 * k] = A[7 * k] - s;
-      for (int i = k + 1; i < n; i++) {
-        s = A[6 * i] * w.temp[0];
-        for (int j = 1; j < k; j++) s = s + A[6 * i + j] * w.temp[j];
-        A[6 * i + k] = A[6 * i + k] - s;
-      }
-    }
-    const double akk = A[7 * k];
-    const bool valid = fabs(akk) > 0.0;
-    if (k == 0 && !valid) {  // the whole diagonal is zero: ZeroSign, isPositive()
-      for (int j = 0; j < n; j++) w.tr[j] = j;
-      return true;
-    }
-    if (valid)
-      for (int i = k + 1; i < n; i++) A[6 * i + k] = A[6 * i + k] / akk;
-    if (sign == 1) {
-      if (akk < 0) sign = 2;
-    } else if (sign == -1) {
-      if (akk > 0) sign = 2;
-    } else if (sign == 0) {
-      if (akk > 0) sign = 1;
-      else if (akk < 0) sign = -1;
-    }
-  }
-  return sign == 1 || sign == 0;
-}
-
-// EIGEN: LDLT::solve on w.rhs into w.x: P b, the unit lower solve by columns, D^-1 (0 where |d| <=
-// DBL_MIN), the transposed solve by dot products summed left to right, P^T. tr[k] is in k..5.
-PO_HD inline void po_ldlt_solve(PoWork& w) {
-  const int n = 6;
-  const double* A = w.A;
-  double* x = w.rhs;
-  double tmp;
-  for (int k = 0; k < n; k++) tmp = x[k], x[k] = x[w.tr[k]], x[w.tr[k]] = tmp;
-  for (int i = 0; i < n; i++)
-    for (int r = i + 1; r < n; r++) x[r] = x[r] - x[i] * A[6 * r + i];
-  for (int i = 0; i < n; i++) x[i] = fabs(A[7 * i]) > DBL_MIN ? x[i] / A[7 * i] : 0.0;
-  for (int i = n - 2; i >= 0; i--) {
-    double s = A[6 * (i + 1) + i] * x[i + 1];
-    for (int j = i + 2; j < n; j++) s = s + A[6 * j + i] * x[j];
-    x[i] = x[i] - s;
-  }
-  for (int k = n - 1; k >= 0; k--) tmp = x[k], x[k] = x[w.tr[k]], x[w.tr[k]] = tmp;
-  for (int i = 0; i < n; i++) w.x[i] = x[i];
-}
-
-PO_HD inline bool po_finite(double v) { return v - v == 0.0; }
-
 // ---- PoseOptimization ------------------------------------------------------------------------------
 // mask: ceil(n / 64) words, bit i % 64 of word i / 64 = mvbOutlier[i]. Lane 0 writes o and mask.
 template <class G>
@@ -535,24 +419,21 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
     const bool kernel_on = it < 3;  // :408: the kernel is removed after round 2
     int n_active = 0;
     for (int c = 0; c < words; c++) n_active += (int)__builtin_popcountll(g.ballot(val, c) & ~g.ballot(out, c));
-    int iterations = 0, trials = 0, rejected = 0, stop = PO_STOP_ALL;
-    double lambda = 0.0, current = 0.0;
+    int iterations = 0, trials = 0, rejected = 0, stop = LM_STOP_ALL;
+    LmCtl lm = {0.0, 0.0, 0.0, 2.0, 0.0, 0, 0};
     if (n_active == 0) {
-      stop = PO_STOP_NO_EDGE;
+      stop = LM_STOP_NO_EDGE;
     } else {
       g.sync();
       if (lane == 0)
         for (int j = 0; j < 6; j++) w.x[j] = 0.0;  // deviation: zero before a round's first successful solve
       g.sync();
-      double ni = 2.0;
-      int nbad_steps = 0;
       for (int i = 0; i < 10; i++) {
         iterations++;
         double S[G::slots][PO_ACC];
         po_sums<true>(g, P, out, est, kernel_on, S);
         const double* s = S[0];
-        const double ini = s[27];
-        current = ini;
+        double lambda_init = 0.0;
         if (i == 0) {
           double mx = 0.0;
 #pragma unroll
@@ -560,13 +441,11 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
             const double a = fabs(s[j * (j + 1) / 2 + j]);
             mx = a < mx ? mx : a;  // std::max(fabs(H_jj), maxDiagonal)
           }
-          lambda = 1e-5 * mx;
-          ni = 2.0;
-          nbad_steps = 0;
+          lambda_init = 1e-5 * mx;
         }
-        double rho = 0.0;
-        int qmax = 0;
+        lm_begin_iteration(lm, s[27], i == 0, lambda_init);
         do {
+          const double lambda = lm.lambda;
           // setLambda + LinearSolverDense::solve. Deviation: a non-finite entry gives ok2 = false
           bool ok2 = true;
 #pragma unroll
@@ -574,7 +453,7 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
           ok2 = ok2 && po_finite(lambda);
 #pragma unroll
           for (int j = 0; j < 6; j++) ok2 = ok2 && po_finite(s[j * (j + 1) / 2 + j] + lambda);
-          if (!ok2) flags |= PO_FLAG_NONFINITE;
+          if (!ok2) flags |= LM_FLAG_NONFINITE;
           g.sync();
           if (lane == 0 && ok2) {
 #pragma unroll
@@ -583,8 +462,8 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
               for (int c = 0; c <= r; c++) w.A[6 * r + c] = r == c ? s[r * (r + 1) / 2 + c] + lambda : s[r * (r + 1) / 2 + c];
               w.rhs[r] = s[21 + r];
             }
-            w.positive = po_ldlt(w) ? 1 : 0;
-            if (w.positive) po_ldlt_solve(w);
+            w.positive = lm_ldlt<6>(w.A, w.tr, w.temp) ? 1 : 0;
+            if (w.positive) lm_ldlt_solve<6>(w.A, w.tr, w.rhs, w.x);
           }
           g.sync();
           ok2 = ok2 && w.positive != 0;
@@ -597,41 +476,15 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
           eval = trial;
           double C[G::slots][1];
           po_sums<false>(g, P, out, trial, kernel_on, C);
-          double temp = C[0][0];
-          if (!ok2) temp = DBL_MAX;
-          rho = current - temp;
           double scale = 0.0;
 #pragma unroll
           for (int j = 0; j < 6; j++) scale = scale + x[j] * (lambda * x[j] + s[21 + j]);
-          scale = scale + 1e-3;
-          rho = rho / scale;
           trials++;
-          if (rho > 0 && po_finite(temp)) {
-            const double y = 2 * rho - 1;
-            double alpha = 1.0 - y * y * y;  // deviation: pow(2 * rho - 1, 3) as x * x * x
-            alpha = 2.0 / 3.0 < alpha ? 2.0 / 3.0 : alpha;
-            const double factor = 1.0 / 3.0 < alpha ? alpha : 1.0 / 3.0;
-            lambda = lambda * factor;
-            ni = 2.0;
-            current = temp;
-            est = trial;
-          } else {
-            lambda = lambda * ni;
-            ni = ni * 2;
-            rejected++;
-          }
-          qmax++;
-        } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) {
-          stop = PO_STOP_TERMINATE;
-          break;
-        }
-        if ((ini - current) * 1e3 < ini) nbad_steps++;
-        else nbad_steps = 0;
-        if (nbad_steps >= 3) {
-          stop = PO_STOP_NBAD;
-          break;
-        }
+          if (lm_trial(lm, C[0][0], !ok2, scale)) est = trial;
+          else rejected++;
+        } while (lm_more_trials(lm));
+        stop = lm_end_iteration(lm);
+        if (stop != LM_STOP_ALL) break;
       }
     }
     // :383-439: an edge flagged before is recomputed at the final estimate, an active one keeps the
@@ -661,7 +514,7 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
     for (int c = 0; c < words; c++) n_bad += (int)__builtin_popcountll(g.ballot(out, c));
     rounds_run = it + 1;
     if (lane == 0) {
-      PoRound r = {n_active, iterations, trials, rejected, stop, n_bad, lambda, current};
+      PoRound r = {n_active, iterations, trials, rejected, stop, n_bad, lm.lambda, lm.current};
       o->rounds[it] = r;
     }
   }

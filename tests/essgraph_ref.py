@@ -17,10 +17,10 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from lm_ref import (DBL_MAX, FLAG_LARGE_STEP, FLAG_NONFINITE, NAN, PO_LANES, STOP_ALL, STOP_NBAD,  # noqa: F401
+                    STOP_NO_EDGE, STOP_TERMINATE, div, finite, levenberg, tree)
 from optsim3_ref import exp, flat, oplus, sim3_inverse, sim3_map, sim3_mul  # noqa: F401
-from poseopt_ref import (DBL_MAX, FLAG_LARGE_STEP, FLAG_NONFINITE, NAN, PO_LANES, STOP_ALL, STOP_NBAD,  # noqa: F401
-                         STOP_NO_EDGE, STOP_TERMINATE, bits64, c_sqrt, div, finite, quat_from_matrix, quat_rotate,
-                         quat_to_matrix, sincos, tree)
+from poseopt_ref import bits64, c_sqrt, quat_from_matrix, quat_rotate, quat_to_matrix, sincos  # noqa: F401
 
 DELTA = 1e-9
 SCALAR = 1.0 / (2 * DELTA)
@@ -457,51 +457,21 @@ class Solver:
 
 def optimize(S, on_iteration=None):
     """SparseOptimizer::optimize(20) with OptimizationAlgorithmLevenberg::solve, lambda from
-    setUserLambdaInit(1e-16) -> the trace"""
-    tr = SimpleNamespace(iterations=0, trials=0, rejected_trials=0, stop=STOP_ALL, lam=0.0, chi2=0.0,
+    setUserLambdaInit(1e-16), no stop flag -> the trace. on_iteration(i, ini, current), if given, sees
+    every iteration's chi2 before and after its trials (tr.chis keeps them)."""
+    tr = SimpleNamespace(iterations=0, trials=0, rejected_trials=0, stop=STOP_NO_EDGE, lam=0.0, chi2=0.0,
                          env_blocks=S.env_blocks, flags=0, chis=[])
     if S.ne == 0:
-        tr.stop = STOP_NO_EDGE
         return tr
-    lam, current, ni, nbad = 0.0, 0.0, 2.0, 0
-    for i in range(MAX_ITER):
-        tr.iterations += 1
-        ini = S.linearize()
-        current = ini
-        if i == 0:
-            lam, ni, nbad = 1e-16, 2.0, 0
-        rho, qmax = 0.0, 0
-        while True:
-            chi, scale, fail = S.trial(lam)
-            temp = DBL_MAX if fail else chi
-            rho = current - temp
-            rho = div(rho, scale + 1e-3)
-            tr.trials += 1
-            if rho > 0 and finite(temp):
-                y = 2 * rho - 1
-                alpha = 1.0 - y * y * y  # DEVIATION: pow(2 * rho - 1, 3) as x * x * x
-                alpha = 2.0 / 3.0 if 2.0 / 3.0 < alpha else alpha
-                factor = alpha if 1.0 / 3.0 < alpha else 1.0 / 3.0
-                lam = lam * factor
-                ni = 2.0
-                current = temp
-                S.accept()
-            else:
-                lam = lam * ni
-                ni = ni * 2
-                tr.rejected_trials += 1
-            qmax += 1
-            if not (rho < 0 and qmax < 10):
-                break
+
+    def each(i, ini, current):
         tr.chis.append((ini, current))
-        if qmax == 10 or rho == 0:
-            tr.stop = STOP_TERMINATE
-            break
-        nbad = nbad + 1 if (ini - current) * 1e3 < ini else 0
-        if nbad >= 3:
-            tr.stop = STOP_NBAD
-            break
-    tr.lam, tr.chi2, tr.flags = lam, current, S.flags
+        if on_iteration:
+            on_iteration(i, ini, current)
+
+    t = levenberg(lambda: (S.linearize(), 0.0), S.trial, S.accept, MAX_ITER, user_lambda=1e-16, on_iteration=each)
+    tr.iterations, tr.trials, tr.rejected_trials, tr.stop = t.iterations, t.trials, t.rejected_trials, t.stop
+    tr.lam, tr.chi2, tr.flags = t.lam, t.chi2, S.flags
     return tr
 
 

@@ -9,11 +9,11 @@ A problem is anything with n_kf, n_points, n_edges, tcw (n_kf, 12), k (n_kf, 4),
 import numpy as np
 
 import poseopt_ref as P
-from poseopt_ref import DBL_MAX, c_sqrt, div, finite
+from lm_ref import (FLAG_LARGE_STEP, FLAG_NONFINITE, STOP_ALL, STOP_FLAG, STOP_NBAD, STOP_NO_EDGE,  # noqa: F401
+                    STOP_TERMINATE, div, finite, levenberg)
+from poseopt_ref import c_sqrt
 
 LANES = 64
-FLAG_LARGE_STEP, FLAG_NONFINITE = 1, 2
-STOP_ALL, STOP_TERMINATE, STOP_NBAD, STOP_NO_EDGE, STOP_FLAG = 0, 1, 2, 3, 4
 TH_MONO, TH_STEREO = 5.991, 7.815
 
 
@@ -490,59 +490,20 @@ class Poller:
 
 
 def optimize_round(S, n_edges, max_it, poll):
-    """SparseOptimizer::optimize(max_it) + OptimizationAlgorithmLevenberg::solve"""
+    """SparseOptimizer::optimize(max_it) + OptimizationAlgorithmLevenberg::solve, lambda from the diagonal"""
     r = Round()
     r.n_active = n_edges
     if n_edges == 0:
         r.stop = STOP_NO_EDGE
         return r
-    lam, current, ni, nbad = 0.0, 0.0, 2.0, 0
-    for i in range(max_it):
-        if poll():
-            r.stop = STOP_FLAG
-            break
-        r.iterations += 1
-        ini, maxdiag = S.linearize()
-        current = ini
-        if i == 0:
-            lam, ni, nbad = 1e-5 * maxdiag, 2.0, 0
-        rho, qmax = 0.0, 0
-        while True:
-            chi, scale, fail = S.trial(lam)
-            temp = DBL_MAX if fail else chi
-            rho = current - temp
-            rho = div(rho, scale + 1e-3)
-            r.trials += 1
-            r.fail_trace.append(fail)
-            if rho > 0 and finite(temp):
-                y = 2 * rho - 1
-                alpha = 1.0 - y * y * y  # DEVIATION: pow(., 3) as x * x * x
-                alpha = 2.0 / 3.0 if 2.0 / 3.0 < alpha else alpha
-                factor = alpha if 1.0 / 3.0 < alpha else 1.0 / 3.0
-                lam = lam * factor
-                ni = 2.0
-                r.chi_trace.append((current, temp, True))
-                current = temp
-                S.accept()
-            else:
-                lam = lam * ni
-                ni = ni * 2
-                r.rejected_trials += 1
-                r.chi_trace.append((current, temp, False))
-            qmax += 1
-            more = rho < 0 and qmax < 10
-            if more and poll():
-                more = False
-            if not more:
-                break
-        if qmax == 10 or rho == 0:
-            r.stop = STOP_TERMINATE
-            break
-        nbad = nbad + 1 if (ini - current) * 1e3 < ini else 0
-        if nbad >= 3:
-            r.stop = STOP_NBAD
-            break
-    r.lam, r.chi2 = lam, current
+
+    def on_trial(current, temp, failed, accepted):
+        r.fail_trace.append(failed)
+        r.chi_trace.append((current, temp, accepted))
+
+    t = levenberg(S.linearize, S.trial, S.accept, max_it, poll=poll, on_trial=on_trial)
+    r.iterations, r.trials, r.rejected_trials, r.stop = t.iterations, t.trials, t.rejected_trials, t.stop
+    r.lam, r.chi2 = t.lam, t.chi2
     return r
 
 

@@ -12,11 +12,14 @@ The sum over edges is fixed: correspondence i (KF1's keypoint index) belongs to 
 e12 then e21 of its active correspondences in ascending i from +0.0, and the lanes are combined by
 s[l] += s[l + stride], stride = 32 .. 1.
 """
+from types import SimpleNamespace
+
 import numpy as np
 
-from poseopt_ref import (DBL_MAX, DBL_MIN, FLAG_LARGE_STEP, FLAG_NONFINITE, NAN, PO_LANES, STOP_ALL, STOP_NBAD,  # noqa: F401
-                         STOP_NO_EDGE, STOP_TERMINATE, Round, bits64, c_sqrt, div, finite, mat3_mul, quat_from_matrix,
-                         quat_mul, quat_rotate, quat_to_matrix, sincos, tree)
+from lm_ref import (DBL_MAX, DBL_MIN, FLAG_LARGE_STEP, FLAG_NONFINITE, NAN, PO_LANES, STOP_ALL, STOP_NBAD,  # noqa: F401
+                    STOP_NO_EDGE, STOP_TERMINATE, div, finite, ldlt, ldlt_solve, levenberg, tree)
+from poseopt_ref import (Round, bits64, c_sqrt, mat3_mul, quat_from_matrix, quat_mul, quat_rotate,  # noqa: F401
+                         quat_to_matrix, sincos)
 
 ACC = 36  # 28 lower entries of H (row-major over r >= c), 7 of b, the robust chi2
 H_IDX = [[r * (r + 1) // 2 + c if c <= r else -1 for c in range(7)] for r in range(7)]
@@ -258,83 +261,7 @@ def sums_chi(pairs, active, S, Si, delta, dsqr):
     return tree(lanes)[0]
 
 
-# ---- the 7x7 solve ---------------------------------------------------------------------------------
-def ldlt(A):
-    """EIGEN: LDLT<MatrixXd, Lower>::compute, unblocked and in place on the lower triangle of the 7x7 A,
-    by section 18's rules. -> (transpositions, is_positive)"""
-    n = 7
-    tr = list(range(n))
-    sign = 0  # ZeroSign; 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
-    temp = [0.0] * n
-    for k in range(n):
-        big, best = k, abs(A[k][k])
-        for j in range(k + 1, n):
-            if abs(A[j][j]) > best:
-                big, best = j, abs(A[j][j])
-        tr[k] = big
-        if k != big:
-            p = big
-            for j in range(k):
-                A[k][j], A[p][j] = A[p][j], A[k][j]
-            for i in range(p + 1, n):
-                A[i][k], A[i][p] = A[i][p], A[i][k]
-            A[k][k], A[p][p] = A[p][p], A[k][k]
-            for i in range(k + 1, p):
-                A[i][k], A[p][i] = A[p][i], A[i][k]
-        if k > 0:
-            for j in range(k):
-                temp[j] = A[j][j] * A[k][j]
-            s = A[k][0] * temp[0]
-            for j in range(1, k):
-                s = s + A[k][j] * temp[j]
-            A[k][k] = A[k][k] - s
-            for i in range(k + 1, n):
-                s = A[i][0] * temp[0]
-                for j in range(1, k):
-                    s = s + A[i][j] * temp[j]
-                A[i][k] = A[i][k] - s
-        akk = A[k][k]
-        valid = abs(akk) > 0.0
-        if k == 0 and not valid:
-            return list(range(n)), True  # the whole diagonal is zero: ZeroSign, isPositive()
-        if valid:
-            for i in range(k + 1, n):
-                A[i][k] = A[i][k] / akk
-        if sign == 1:
-            if akk < 0:
-                sign = 2
-        elif sign == -1:
-            if akk > 0:
-                sign = 2
-        elif sign == 0:
-            if akk > 0:
-                sign = 1
-            elif akk < 0:
-                sign = -1
-    return tr, sign == 1 or sign == 0
-
-
-def ldlt_solve(A, tr, b):
-    """EIGEN: LDLT::solve, as section 18 with n = 7"""
-    n = 7
-    x = list(b)
-    for k in range(n):
-        x[k], x[tr[k]] = x[tr[k]], x[k]
-    for i in range(n):
-        for r in range(i + 1, n):
-            x[r] = x[r] - x[i] * A[r][i]
-    for i in range(n):
-        x[i] = x[i] / A[i][i] if abs(A[i][i]) > DBL_MIN else 0.0
-    for i in range(n - 2, -1, -1):
-        s = A[i + 1][i] * x[i + 1]
-        for j in range(i + 2, n):
-            s = s + A[j][i] * x[j]
-        x[i] = x[i] - s
-    for k in range(n - 1, -1, -1):
-        x[k], x[tr[k]] = x[tr[k]], x[k]
-    return x
-
-
+# ---- the 7x7 solve (lm_ref.ldlt / ldlt_solve) ------------------------------------------------------
 def system_of(S, lam):
     """H + lambda I (lower triangle) and b of the sums S"""
     A = [[0.0] * 7 for _ in range(7)]
@@ -405,70 +332,39 @@ def optimize(p, hook=None):
         if not active:
             R.stop = STOP_NO_EDGE
         else:
-            x = [0.0] * 7  # DEVIATION: zero before a round's first successful solve
-            lam, ni, n_bad = 0.0, 2.0, 0
-            current = 0.0
-            for i in range(max_iter):
-                R.iterations += 1
-                tab = build_table(est, fix_scale)
-                S = sums_full(pairs, active, tab, delta, dsqr)
-                current = ini = S[35]
-                if i == 0:
-                    mx = 0.0
-                    for j in range(7):
-                        a = abs(S[H_IDX[j][j]])
-                        mx = mx if a < mx else a  # std::max(fabs(H_jj), maxDiagonal)
-                    lam, ni, n_bad = 1e-5 * mx, 2.0, 0
-                if hook:
-                    hook(it, i, S, lam)
-                rho, qmax = 0.0, 0
-                while True:
-                    ok2, x, fl = solve_step(S, lam, x)
-                    res.flags |= fl
-                    x = list(x)
-                    trial, fl = oplus(x, fix_scale, est)  # zeroes x[6] with fix_scale: computeScale reads it so
-                    res.flags |= fl
-                    trial_inv = sim3_inverse(trial)
-                    T_eval = trial
-                    temp = sums_chi(pairs, active, trial, trial_inv, delta, dsqr)
-                    if not ok2:
-                        temp = DBL_MAX
-                    rho = current - temp
-                    scale = 0.0
-                    for j in range(7):
-                        scale = scale + x[j] * (lam * x[j] + S[28 + j])
-                    scale = scale + 1e-3
-                    rho = div(rho, scale)
-                    R.trials += 1
-                    if rho > 0 and finite(temp):
-                        y = 2 * rho - 1
-                        alpha = 1.0 - y * y * y  # DEVIATION: pow(2 * rho - 1, 3) as x * x * x
-                        alpha = 2.0 / 3.0 if 2.0 / 3.0 < alpha else alpha
-                        factor = alpha if 1.0 / 3.0 < alpha else 1.0 / 3.0
-                        lam = lam * factor
-                        ni = 2.0
-                        current = temp
-                        est = trial
-                        R.last_rejected = False
-                    else:
-                        lam = lam * ni
-                        ni = ni * 2
-                        R.rejected_trials += 1
-                        R.last_rejected = True
-                    qmax += 1
-                    if not (rho < 0 and qmax < 10):
-                        break
-                if qmax == 10 or rho == 0:
-                    R.stop = STOP_TERMINATE
-                    break
-                if (ini - current) * 1e3 < ini:
-                    n_bad += 1
-                else:
-                    n_bad = 0
-                if n_bad >= 3:
-                    R.stop = STOP_NBAD
-                    break
-            R.lam, R.chi2 = lam, current
+            # DEVIATION: x is zero before a round's first successful solve
+            st = SimpleNamespace(x=[0.0] * 7, S=None, trial=None)
+
+            def linearize():
+                st.S = sums_full(pairs, active, build_table(est, fix_scale), delta, dsqr)
+                mx = 0.0
+                for j in range(7):
+                    a = abs(st.S[H_IDX[j][j]])
+                    mx = mx if a < mx else a  # std::max(fabs(H_jj), maxDiagonal)
+                return st.S[35], mx
+
+            def trial(lam):
+                nonlocal T_eval
+                ok2, x, fl = solve_step(st.S, lam, st.x)
+                res.flags |= fl
+                st.x = list(x)
+                st.trial, fl = oplus(st.x, fix_scale, est)  # zeroes x[6] with fix_scale: computeScale reads it so
+                res.flags |= fl
+                T_eval = st.trial
+                temp = sums_chi(pairs, active, st.trial, sim3_inverse(st.trial), delta, dsqr)
+                scale = 0.0
+                for j in range(7):
+                    scale = scale + st.x[j] * (lam * st.x[j] + st.S[28 + j])
+                return temp, scale, not ok2
+
+            def accept():
+                nonlocal est
+                est = st.trial
+
+            t = levenberg(linearize, trial, accept, max_iter,
+                          on_lambda=(lambda i, lam: hook(it, i, st.S, lam)) if hook else None)
+            R.iterations, R.trials, R.rejected_trials, R.stop = t.iterations, t.trials, t.rejected_trials, t.stop
+            R.lam, R.chi2, R.last_rejected = t.lam, t.chi2, t.last_rejected
         T_inv = sim3_inverse(T_eval)
         for i in active:
             res.removed[i] = classify(pairs[i], T_eval, T_inv, th2)

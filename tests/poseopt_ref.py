@@ -14,22 +14,17 @@ ascending i from +0.0, and the lanes are combined by s[l] += s[l + stride], stri
 """
 import math
 import struct
+from types import SimpleNamespace
 
 import numpy as np
 
-PO_LANES = 64
-FLAG_LARGE_STEP = 1  # ORBFE_POSEOPT_FLAG_LARGE_STEP: sin / cos of a theta above pi
-FLAG_NONFINITE = 2   # ORBFE_POSEOPT_FLAG_NONFINITE: a non-finite entry of H + lambda I or b
-DBL_MAX = 1.7976931348623157e308
-DBL_MIN = 2.2250738585072014e-308
-NAN = float("nan")
+from lm_ref import (DBL_MAX, DBL_MIN, FLAG_LARGE_STEP, FLAG_NONFINITE, NAN, PO_LANES, STOP_ALL, STOP_NBAD,  # noqa: F401
+                    STOP_NO_EDGE, STOP_TERMINATE, div, finite, ldlt, ldlt_solve, levenberg, tree)
 
 DELTA_MONO = float(np.float32(math.sqrt(5.991)))    # const float deltaMono = sqrt(5.991), setDelta widens
 DELTA_STEREO = float(np.float32(math.sqrt(7.815)))
 CHI2_MONO = np.float32(5.991)
 CHI2_STEREO = np.float32(7.815)
-
-STOP_ALL, STOP_TERMINATE, STOP_NBAD, STOP_NO_EDGE = 0, 1, 2, 3
 
 # ---- sin / cos from + - * / ------------------------------------------------------------------------
 PI = 3.141592653589793
@@ -241,16 +236,6 @@ def se3_to_tcw(T):
 
 
 # ---- one edge --------------------------------------------------------------------------------------
-def div(a, b):
-    """IEEE division (Python raises on a zero divisor)"""
-    if b == 0.0:
-        if a != a or a == 0.0:
-            return NAN
-        neg = (math.copysign(1.0, a) < 0) != (math.copysign(1.0, b) < 0)
-        return -math.inf if neg else math.inf
-    return a / b
-
-
 class Edge:
     """One correspondence: Xw, obs, the camera and invSigma2 as the doubles the reference widens to."""
 
@@ -345,17 +330,6 @@ def edge_accumulate(acc, e, T, kernel_on, full):
             acc[H_IDX[r][c]] = acc[H_IDX[r][c]] + s
 
 
-def tree(lanes):
-    """the fixed combination of the PO_LANES lane accumulators"""
-    s = [list(l) for l in lanes]
-    stride = PO_LANES // 2
-    while stride >= 1:
-        for l in range(stride):
-            s[l] = [a + b for a, b in zip(s[l], s[l + stride])]
-        stride //= 2
-    return s[0]
-
-
 def sums(edges, active, T, kernel_on, full):
     """edges: {i: Edge}; active: ascending keypoint indices -> the 28 sums"""
     lanes = [[0.0] * ACC for _ in range(PO_LANES)]
@@ -364,89 +338,7 @@ def sums(edges, active, T, kernel_on, full):
     return tree(lanes)
 
 
-# ---- the 6x6 solve ---------------------------------------------------------------------------------
-def ldlt(A):
-    """EIGEN: LDLT<MatrixXd, Lower>::compute, unblocked and in place on the lower triangle of the 6x6
-    A (list of rows, only r >= c read or written). Pivot: the largest |diagonal| of the trailing part,
-    the first maximum wins. -> (transpositions, is_positive)"""
-    n = 6
-    tr = list(range(n))
-    sign = 0  # ZeroSign; 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite
-    temp = [0.0] * n
-    for k in range(n):
-        big, best = k, abs(A[k][k])
-        for j in range(k + 1, n):
-            if abs(A[j][j]) > best:
-                big, best = j, abs(A[j][j])
-        tr[k] = big
-        if k != big:
-            p = big
-            for j in range(k):
-                A[k][j], A[p][j] = A[p][j], A[k][j]
-            for i in range(p + 1, n):
-                A[i][k], A[i][p] = A[i][p], A[i][k]
-            A[k][k], A[p][p] = A[p][p], A[k][k]
-            for i in range(k + 1, p):
-                A[i][k], A[p][i] = A[p][i], A[i][k]
-        if k > 0:
-            for j in range(k):
-                temp[j] = A[j][j] * A[k][j]
-            s = A[k][0] * temp[0]
-            for j in range(1, k):
-                s = s + A[k][j] * temp[j]
-            A[k][k] = A[k][k] - s
-            for i in range(k + 1, n):
-                s = A[i][0] * temp[0]
-                for j in range(1, k):
-                    s = s + A[i][j] * temp[j]
-                A[i][k] = A[i][k] - s
-        akk = A[k][k]
-        valid = abs(akk) > 0.0
-        if k == 0 and not valid:
-            return list(range(n)), True  # the whole diagonal is zero: ZeroSign, isPositive()
-        if valid:
-            for i in range(k + 1, n):
-                A[i][k] = A[i][k] / akk
-        if sign == 1:
-            if akk < 0:
-                sign = 2
-        elif sign == -1:
-            if akk > 0:
-                sign = 2
-        elif sign == 0:
-            if akk > 0:
-                sign = 1
-            elif akk < 0:
-                sign = -1
-    return tr, sign == 1 or sign == 0
-
-
-def ldlt_solve(A, tr, b):
-    """EIGEN: LDLT::solve: P b, the unit lower solve by columns, D^-1 (0 where |d| <= DBL_MIN), the
-    transposed solve by dot products summed left to right, P^T"""
-    n = 6
-    x = list(b)
-    for k in range(n):
-        x[k], x[tr[k]] = x[tr[k]], x[k]
-    for i in range(n):
-        for r in range(i + 1, n):
-            x[r] = x[r] - x[i] * A[r][i]
-    for i in range(n):
-        x[i] = x[i] / A[i][i] if abs(A[i][i]) > DBL_MIN else 0.0
-    for i in range(n - 2, -1, -1):
-        s = A[i + 1][i] * x[i + 1]
-        for j in range(i + 2, n):
-            s = s + A[j][i] * x[j]
-        x[i] = x[i] - s
-    for k in range(n - 1, -1, -1):
-        x[k], x[tr[k]] = x[tr[k]], x[k]
-    return x
-
-
-def finite(v):
-    return v - v == 0.0
-
-
+# ---- the 6x6 solve (lm_ref.ldlt / ldlt_solve) ------------------------------------------------------
 def solve_step(S, lam, x_prev):
     """setLambda + LinearSolverDense::solve on the sums S -> (ok2, x, flags).
     DEVIATION: a non-finite entry of H + lambda I or b gives ok2 = false (FLAG_NONFINITE) without a
@@ -525,66 +417,37 @@ def optimize(n, valid, xw, kp_un, u_right, inv_sigma2, k, bf, tcw):
         if not active:
             R.stop = STOP_NO_EDGE
         else:
-            x = [0.0] * 6  # DEVIATION: zero before a round's first successful solve
-            lam, ni, n_bad = 0.0, 2.0, 0
-            current = 0.0
-            for i in range(10):
-                R.iterations += 1
-                S = sums(edges, active, est, kernel_on, True)
-                current = ini = S[27]
-                if i == 0:
-                    mx = 0.0
-                    for j in range(6):
-                        a = abs(S[H_IDX[j][j]])
-                        mx = mx if a < mx else a  # std::max(fabs(H_jj), maxDiagonal)
-                    lam, ni, n_bad = 1e-5 * mx, 2.0, 0
-                rho, qmax = 0.0, 0
-                while True:
-                    ok2, x, fl = solve_step(S, lam, x)
-                    res.flags |= fl
-                    dq, dt, fl = se3_exp(x)
-                    res.flags |= fl
-                    trial = se3_mul((dq, dt), est)
-                    T_eval = trial
-                    temp = sums(edges, active, trial, kernel_on, False)[27]
-                    if not ok2:
-                        temp = DBL_MAX
-                    rho = current - temp
-                    scale = 0.0
-                    for j in range(6):
-                        scale = scale + x[j] * (lam * x[j] + S[21 + j])
-                    scale = scale + 1e-3
-                    rho = div(rho, scale)
-                    R.trials += 1
-                    if rho > 0 and finite(temp):
-                        y = 2 * rho - 1
-                        alpha = 1.0 - y * y * y  # DEVIATION: pow(2 * rho - 1, 3) as x * x * x
-                        alpha = 2.0 / 3.0 if 2.0 / 3.0 < alpha else alpha
-                        factor = alpha if 1.0 / 3.0 < alpha else 1.0 / 3.0
-                        lam = lam * factor
-                        ni = 2.0
-                        current = temp
-                        est = trial
-                        R.last_rejected = False
-                    else:
-                        lam = lam * ni
-                        ni = ni * 2
-                        R.rejected_trials += 1
-                        R.last_rejected = True
-                    qmax += 1
-                    if not (rho < 0 and qmax < 10):
-                        break
-                if qmax == 10 or rho == 0:
-                    R.stop = STOP_TERMINATE
-                    break
-                if (ini - current) * 1e3 < ini:
-                    n_bad += 1
-                else:
-                    n_bad = 0
-                if n_bad >= 3:
-                    R.stop = STOP_NBAD
-                    break
-            R.lam, R.chi2 = lam, current
+            # DEVIATION: x is zero before a round's first successful solve
+            st = SimpleNamespace(x=[0.0] * 6, S=None, trial=None)
+
+            def linearize():
+                st.S = sums(edges, active, est, kernel_on, True)
+                mx = 0.0
+                for j in range(6):
+                    a = abs(st.S[H_IDX[j][j]])
+                    mx = mx if a < mx else a  # std::max(fabs(H_jj), maxDiagonal)
+                return st.S[27], mx
+
+            def trial(lam):
+                nonlocal T_eval
+                ok2, st.x, fl = solve_step(st.S, lam, st.x)
+                res.flags |= fl
+                dq, dt, fl = se3_exp(st.x)
+                res.flags |= fl
+                st.trial = T_eval = se3_mul((dq, dt), est)
+                temp = sums(edges, active, st.trial, kernel_on, False)[27]
+                scale = 0.0
+                for j in range(6):
+                    scale = scale + st.x[j] * (lam * st.x[j] + st.S[21 + j])
+                return temp, scale, not ok2
+
+            def accept():
+                nonlocal est
+                est = st.trial
+
+            t = levenberg(linearize, trial, accept, 10)
+            R.iterations, R.trials, R.rejected_trials, R.stop = t.iterations, t.trials, t.rejected_trials, t.stop
+            R.lam, R.chi2, R.last_rejected = t.lam, t.chi2, t.last_rejected
         for i in idx:
             res.outlier[i] = classify(edges[i], est, T_eval, bool(res.outlier[i]))
         R.outlier = res.outlier.copy()
