@@ -10,8 +10,8 @@
  * BaseBinaryEdge::constructQuadraticForm, RobustKernelHuber, BlockSolver_6_3 (buildSystem, setLambda,
  * restoreDiagonal, the Schur branch of solve), OptimizationAlgorithmLevenberg (solve,
  * computeLambdaInit, computeScale) and SparseOptimizer (initializeOptimization(level), optimize, push,
- * pop, discardTop, update, activeRobustChi2). BundleAdjustment / GlobalBundleAdjustemnt is not covered:
- * its reduced system is not dense-solvable. OptimizeEssentialGraph is orbfe_essgraph.h.
+ * pop, discardTop, update, activeRobustChi2). BundleAdjustment / GlobalBundleAdjustemnt, whose reduced
+ * system is not dense-solvable, is orbfe_gba.h. OptimizeEssentialGraph is orbfe_essgraph.h.
  *
  * The caller performs the gather of Optimizer.cc:456-656: the keyframes
  * (local ones, then fixed cameras, each ascending in mnId) with GetPose(), fx fy cx cy, mbf and

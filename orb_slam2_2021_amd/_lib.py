@@ -1,7 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h).
+orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -221,6 +221,29 @@ class lba_result(Structure):
 
 
 LBA_MAX_FREE_KF, LBA_MAX_KF, LBA_MAX_POINTS, LBA_MAX_EDGES = 128, 512, 16384, 131072  # orbfe_lba.h
+
+
+class gba_problem(Structure):  # orbfe_gba.h
+    _fields_ = [("n_kf", c_int), ("n_points", c_int), ("n_edges", c_int), ("tcw", c_void_p), ("k", c_void_p),
+                ("bf", c_void_p), ("fixed", c_void_p), ("xw", c_void_p), ("edge_begin", c_void_p), ("edge_kf", c_void_p),
+                ("kp_un", c_void_p), ("u_right", c_void_p), ("inv_sigma2", c_void_p), ("n_iterations", c_int),
+                ("robust", c_int), ("stop_flag", c_void_p), ("stop_at_poll", c_int)]
+
+
+class gba_trace(Structure):
+    _fields_ = [("n_active", c_int), ("iterations", c_int), ("trials", c_int), ("rejected_trials", c_int),
+                ("stop", c_int), ("lam", c_double), ("chi2", c_double), ("env_blocks", c_int), ("schur_blocks", c_int),
+                ("flags", c_uint32), ("polls", c_int)]
+
+
+class gba_result(Structure):
+    _fields_ = [("tcw", c_void_p), ("xw", c_void_p), ("trace", gba_trace)]
+
+
+GBA_MAX_KF, GBA_MAX_POINTS, GBA_MAX_EDGES, GBA_MAX_ENV_BLOCKS = 4096, 524288, 4194304, 2097152  # orbfe_gba.h
+GBA_MAX_ITERATIONS = 64
+GBA_FLAG_LARGE_STEP, GBA_FLAG_NONFINITE = 1, 2
+GBA_STOP_ALL, GBA_STOP_TERMINATE, GBA_STOP_NBAD, GBA_STOP_NO_EDGE, GBA_STOP_FLAG = 0, 1, 2, 3, 4
 
 
 class essgraph_problem(Structure):  # orbfe_essgraph.h
@@ -458,6 +481,11 @@ _SIGNATURES = {
     "orbfe_lba_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_lba_destroy": (c_int, [c_void_p]),
     "orbfe_lba_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
+    # orbfe_gba.h
+    "orbfe_gba_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_gba_destroy": (c_int, [c_void_p]),
+    "orbfe_gba_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "orbfe_gba_envelope": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     # orbfe_essgraph.h
     "orbfe_essgraph_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_essgraph_destroy": (c_int, [c_void_p]),

@@ -313,6 +313,7 @@ struct LbaDevBackend {
   int start(const LbaPlan& P) {
     w = h->w;
     w.nk = P.nk, w.nfree = P.nfree, w.np = P.np, w.ne = P.ne, w.nslot = 0, w.kernel_on = 1;
+    lba_set_deltas(&w);
     int st;
 #define LBA_UP(dst, src, count) \
   if ((st = up(dst, src, count)) != ORBFE_OK) return st

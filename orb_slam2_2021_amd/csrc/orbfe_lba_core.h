@@ -39,6 +39,7 @@ struct LbaRound {
 
 struct LbaWs {
   int nk, nfree, np, ne, nslot, kernel_on;
+  double delta_mono, delta_stereo;  // RobustKernelHuber's deltas (lba_set_deltas; orbfe_gba_core.h sets its own)
   // the problem, widened to double
   const double* cam;        // [nk * 5] fx fy cx cy bf
   const int* kf_free;       // [nk] index among the free keyframes, or -1
@@ -163,8 +164,7 @@ PO_HD inline void lba_jacobians(const double* cam, bool stereo, const double* q,
   }
 }
 
-PO_HD inline void lba_huber(double chi2, bool stereo, double* rho0, double* rho1) {
-  const double delta = stereo ? (double)(float)sqrt(7.815) : (double)(float)sqrt(5.991);
+PO_HD inline void lba_huber(double chi2, double delta, double* rho0, double* rho1) {
   const double dsqr = delta * delta;
   *rho0 = chi2, *rho1 = 1.0;
   if (!(chi2 <= dsqr)) {  // RobustKernelHuber::robustify
@@ -195,7 +195,7 @@ PO_HD inline void lba_edge(const LbaWs& w, int e, bool trial) {
   for (int k = 0; k < 3; k++) w.e_err[3 * (size_t)e + k] = err[k];
   const double chi2 = lba_chi2(wt, stereo, err);
   double rho0 = chi2, rho1 = 1.0;
-  if (w.kernel_on) lba_huber(chi2, stereo, &rho0, &rho1);
+  if (w.kernel_on) lba_huber(chi2, stereo ? w.delta_stereo : w.delta_mono, &rho0, &rho1);
   double* o = w.e_prod + LBA_EDGE_DOUBLES * (size_t)e;
   o[0] = rho0;
   if (!FULL) return;
@@ -497,6 +497,9 @@ PO_HD inline bool lba_edge_flag(const LbaWs& w, int e) {
   return chi2 > (stereo ? 7.815 : 5.991) || !(p[2] > 0.0);
 }
 
+// Optimizer.cc:520-521: const float thHuberMono = sqrt(5.991), thHuberStereo = sqrt(7.815)
+inline void lba_set_deltas(LbaWs* w) { w->delta_mono = (double)(float)sqrt(5.991), w->delta_stereo = (double)(float)sqrt(7.815); }
+
 // ---- the host side: the plan, the Levenberg control flow, the host backend -------------------------
 struct LbaIn {
   int nk, np, ne;
@@ -696,6 +699,7 @@ struct LbaHostBackend {
     w.bs = bs.data(), w.Lm = Lm.data(), w.Mm = Mm.data(), w.d = d.data(), w.y = y.data(), w.xp = xp.data();
     w.edge_begin = plan.edge_begin, w.e_kf = plan.e_kf;
     w.rec = &rec;
+    lba_set_deltas(&w);
     return 0;
   }
 
