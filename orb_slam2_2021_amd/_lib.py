@@ -1,7 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h).
+orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -171,6 +171,26 @@ class pnp_iterate(Structure):
 
 
 PNP_FLAG_SVD_NULL, PNP_FLAG_QR_SINGULAR = 1, 2  # orbfe_pnp.h: deviation flags of one hypothesis
+
+
+class init_problem(Structure):  # orbfe_init.h
+    _fields_ = [("n1", c_int), ("n2", c_int), ("keys1", c_void_p), ("keys2", c_void_p), ("matches12", c_void_p),
+                ("k", c_float * 4), ("sigma", c_float), ("min_parallax", c_float), ("n_hyp", c_int),
+                ("rand_idx", c_void_p)]
+
+
+class init_result(Structure):
+    _fields_ = [("hyp_capacity", c_int), ("mask_words", c_int), ("p3d", c_void_p), ("triangulated", c_void_p),
+                ("score_h", c_void_p), ("score_f", c_void_p), ("mask_h", c_void_p), ("mask_f", c_void_p),
+                ("ok", c_int), ("r21", c_float * 9), ("t21", c_float * 3), ("n_matches", c_int), ("flags", c_uint32),
+                ("sh", c_float), ("sf", c_float), ("rh", c_float), ("model", c_int), ("best_h", c_int),
+                ("best_f", c_int), ("h21", c_float * 9), ("f21", c_float * 9), ("n_motions", c_int),
+                ("n_good", c_int * 8), ("cos_parallax", c_float * 8), ("candidate", c_int), ("motion", c_int),
+                ("parallax", c_float)]
+
+
+INIT_FLAG_TOO_FEW, INIT_FLAG_NO_MODEL = 1, 2  # orbfe_init.h: deviation flags of one problem
+INIT_MODEL_NONE, INIT_MODEL_H, INIT_MODEL_F = -1, 0, 1
 
 
 class poseopt_problem(Structure):  # orbfe_poseopt.h
@@ -473,6 +493,10 @@ _SIGNATURES = {
     "orbfe_pnp_destroy": (c_int, [c_void_p]),
     "orbfe_pnp_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "orbfe_pnp_iterate": (c_int, [c_void_p, c_int, c_int, POINTER(pnp_state), POINTER(pnp_iterate)]),
+    # orbfe_init.h
+    "orbfe_init_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_init_destroy": (c_int, [c_void_p]),
+    "orbfe_init_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     # orbfe_poseopt.h
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),
