@@ -1,5 +1,9 @@
 """Known-answer tests pinning the CPU oracle to the reference's own tables and to the published
-OpenCV algorithms it restates. CPU only."""
+OpenCV algorithms it restates. CPU only.
+
+The stages' mathematical definitions, with derived bounds where OpenCV's fixed point rounds, are pinned
+by test_definition_oracle.py; OpenCV's exact fixed-point rounding is pinned by neither, and only a
+reference-held vector could pin it."""
 import hashlib
 import math
 import os
