@@ -406,6 +406,7 @@ struct OrbfeStereoScratch {
   size_t io_n = 0;
   uint8_t* h_stage = nullptr;
   size_t h_stage_n = 0;
+  hipError_t rows_attr = hipSuccess;  // k_stereo_rows' dynamic LDS limit raised (scratch_of)
 };
 
 void orbfe_internal_stereo_free(OrbfeStereoScratch* s) {
@@ -423,7 +424,14 @@ void orbfe_internal_stereo_free(OrbfeStereoScratch* s) {
 
 static OrbfeStereoScratch* scratch_of(orbfe_extractor* h) {
   OrbfeStereoScratch** slot = orbfe_internal_stereo_slot(h);
-  if (!*slot) *slot = new OrbfeStereoScratch();
+  if (!*slot) {
+    *slot = new OrbfeStereoScratch();
+    // a row table of more than 16368 ints and its 16 ints of scan scratch pass the 64 KiB a launch
+    // may ask for unannounced: up to 65,600 B of the CU's 160 KiB (callers have set the device)
+    (*slot)->rows_attr = hipFuncSetAttribute((const void*)k_stereo_rows, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(sizeof(int) * (ST_TAB_MAX + 16)));
+    if ((*slot)->rows_attr != hipSuccess) (void)hipGetLastError();
+  }
   return *slot;
 }
 
@@ -493,6 +501,8 @@ static int launch_stereo(OrbfeStereoScratch* S, const OrbfePyramid& PL, int pl0,
   }
   if (g.nbk == 1) g.rbo[0] = rb_all;
   const size_t lds = sizeof(int) * (g.nbk * (g.rows0 + 1) + 16);
+  if (lds > 64 * 1024 && S->rows_attr != hipSuccess)
+    return orbfe_set_error(ORBFE_ERR_HIP, "k_stereo_rows: more than 64 KiB of LDS refused");
   ORBFE_LAUNCH("k_stereo_rows", k_stereo_rows, dim3(n_pairs), dim3(ROWS_THREADS), lds, s, g, d_kps, d_counts,
                      S->d_row_start, S->d_buckets);
   ORBFE_HIP_CHECK(hipGetLastError());
