@@ -166,7 +166,9 @@ class RefExtractor:
         if img.size == 0:
             return np.zeros(0, KEYPOINT_DTYPE), None
         rows, cols = img.shape
-        cap = self.nfeatures + 64 * self.nlevels
+        # a level keeps at most max(budget + 3, 4 * nIni) keys, nIni <= 64 (a first pass over 64
+        # initial nodes is unchecked against the budget)
+        cap = self.nfeatures + 256 * self.nlevels
         kps = np.zeros(cap, KEYPOINT_DTYPE)
         desc = np.zeros((cap, 32), np.uint8)
         n = c_int()
