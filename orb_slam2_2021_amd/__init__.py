@@ -7,6 +7,7 @@ from ._lib import (KEYPOINT_DTYPE, LIB_PATH, LibraryMissing, OrbfeError, ORBFE_M
                    ORBFE_MP_OBSERVED, ORBFE_MP_PRESENT, ORBFE_RESIZE_SCALAR, ORBFE_RESIZE_SIMD128,
                    MPF_BAD, MPF_OBSERVED, MPF_OUTLIER, MPF_PRESENT, MPF_SEEN, MPF_SKIP,
                    MPF_TRACK_IN_VIEW)
+from .covisibility import CovisibilityGraph
 from .essential_graph import EssentialGraphOptimizer, OptimizeEssentialGraph, problem_of_essential_graph
 from .extractor import ORBextractor, register_host, synth_frame, synth_sequence_frame, unregister_host
 from .frames import (DeviceTriKeyFrame, FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
@@ -21,7 +22,7 @@ from .pose_optimization import PoseOptimization, PoseOptimizer
 from .sim3_optimization import OptimizeSim3, Sim3Optimizer, problem_of_keyframes
 from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
-__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "Initializer", "InitializerBatch", "PoseOptimizer", "PoseOptimization", "Sim3Optimizer", "OptimizeSim3", "problem_of_keyframes", "LocalBundleAdjuster", "LocalBundleAdjustment", "problem_of_local_map", "GlobalBundleAdjuster", "GlobalBundleAdjustment", "problem_of_map", "EssentialGraphOptimizer", "OptimizeEssentialGraph", "problem_of_essential_graph", "Frame", "KeyFrame",
+__all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "CovisibilityGraph", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "Initializer", "InitializerBatch", "PoseOptimizer", "PoseOptimization", "Sim3Optimizer", "OptimizeSim3", "problem_of_keyframes", "LocalBundleAdjuster", "LocalBundleAdjustment", "problem_of_local_map", "GlobalBundleAdjuster", "GlobalBundleAdjustment", "problem_of_map", "EssentialGraphOptimizer", "OptimizeEssentialGraph", "problem_of_essential_graph", "Frame", "KeyFrame",
            "TriKeyFrame", "DeviceTriKeyFrame",
            "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

@@ -1,7 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h).
+orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -116,6 +116,23 @@ class kfdb_result(Structure):
     _fields_ = [("capacity", c_int), ("n_sharing", c_int), ("max_common", c_int), ("min_common", c_int),
                 ("kf_ids", c_void_p), ("common_words", c_void_p), ("scored", c_void_p),
                 ("scores", c_void_p), ("n_candidates", c_int), ("candidates", c_void_p)]
+
+
+class covis_connections(Structure):  # orbfe_covis.h
+    _fields_ = [("capacity", c_int), ("n_counter", c_void_p), ("counter_ids", c_void_p),
+                ("counter_weights", c_void_p), ("n_ordered", c_void_p), ("ordered_ids", c_void_p),
+                ("ordered_weights", c_void_p), ("nmax", c_void_p), ("kf_max", c_void_p), ("unchanged", c_void_p)]
+
+
+class covis_votes(Structure):
+    _fields_ = [("capacity", c_int), ("n", c_void_p), ("kf_ids", c_void_p), ("counts", c_void_p),
+                ("max", c_void_p), ("kf_max", c_void_p)]
+
+
+class covis_local_map(Structure):
+    _fields_ = [("point_capacity", c_int), ("fixed_capacity", c_int), ("edge_capacity", c_int),
+                ("n_points", c_int), ("n_fixed", c_int), ("n_edges", c_int), ("point_ids", c_void_p),
+                ("fixed_ids", c_void_p), ("edge_begin", c_void_p), ("edge_kf", c_void_p), ("edge_slot", c_void_p)]
 
 
 class sim3_solver(Structure):  # orbfe_sim3.h
@@ -497,6 +514,18 @@ _SIGNATURES = {
     "orbfe_init_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_init_destroy": (c_int, [c_void_p]),
     "orbfe_init_solve_batch": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    # orbfe_covis.h
+    "orbfe_covis_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_covis_destroy": (c_int, [c_void_p]),
+    "orbfe_covis_set_keyframe": (c_int, [c_void_p, ctypes.c_int64, c_uint64, c_int, c_void_p]),
+    "orbfe_covis_set_slots": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p, c_void_p]),
+    "orbfe_covis_erase_keyframe": (c_int, [c_void_p, ctypes.c_int64]),
+    "orbfe_covis_set_points_bad": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+    "orbfe_covis_clear": (c_int, [c_void_p]),
+    "orbfe_covis_size": (c_int, [c_void_p, POINTER(c_int)]),
+    "orbfe_covis_update_connections": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(covis_connections)]),
+    "orbfe_covis_vote": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(covis_votes)]),
+    "orbfe_covis_local_map": (c_int, [c_void_p, c_int, c_void_p, POINTER(covis_local_map)]),
     # orbfe_poseopt.h
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),

@@ -1,0 +1,310 @@
+"""The covisibility graph on MI355X (include/orbfe_covis.h): the keyframes' mvpMapPoints rows stay on
+the device, and KeyFrame::UpdateConnections, Tracking::UpdateLocalKeyFrames' vote and
+LocalBundleAdjustment's gather run over them there.
+
+`CovisibilityGraph` owns the device table and the graph state the reference keeps in KeyFrame
+(mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, mvOrderedWeights, mpParent, mspChildrens,
+mbFirstConnection). The device returns the counts and orders of src/KeyFrame.cc:304-378; the side
+effects (:360-392, AddConnection / UpdateBestCovisibles at :122-157) are applied here on the host,
+keyframe by keyframe. Keyframes are named by mnId; every order among equal weights is the tie
+key's (the reference's KeyFrame* value; mnId unless given).
+"""
+from __future__ import annotations
+
+from ctypes import byref, c_int, c_void_p
+from types import SimpleNamespace
+from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple
+
+import numpy as np
+
+from . import _lib as L
+
+
+class _Node:
+    """One keyframe's graph state."""
+
+    __slots__ = ("tie_key", "weights", "ordered", "ordered_weights", "parent", "children", "first_connection")
+
+    def __init__(self, tie_key: int):
+        self.tie_key = tie_key
+        self.weights: Dict[int, int] = {}      # mConnectedKeyFrameWeights
+        self.ordered: List[int] = []           # mvpOrderedConnectedKeyFrames
+        self.ordered_weights: List[int] = []   # mvOrderedWeights
+        self.parent: Optional[int] = None      # mpParent
+        self.children: Set[int] = set()        # mspChildrens
+        self.first_connection = True           # mbFirstConnection
+
+
+class CovisibilityGraph:
+    def __init__(self, max_keyframes: int = 4096, max_slots: int = 2048, max_point_id: int = 1 << 20, kfdb=None,
+                 device: int = 0):
+        self._lib = L.lib()
+        h = c_void_p()
+        L.check(self._lib.orbfe_covis_create(int(device), int(max_keyframes), int(max_slots), int(max_point_id),
+                                             byref(h)), "orbfe_covis_create")
+        self._h = h
+        self._kfdb = kfdb
+        self._nodes: Dict[int, _Node] = {}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.orbfe_covis_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        n = c_int()
+        L.check(self._lib.orbfe_covis_size(self._h, byref(n)), "orbfe_covis_size")
+        return n.value
+
+    def __contains__(self, kf_id: int) -> bool:
+        return int(kf_id) in self._nodes
+
+    # ---- the table ----------------------------------------------------------------------------
+    def set_keyframe(self, kf_id: int, point_ids, tie_key: Optional[int] = None) -> None:
+        """Adds a keyframe with its mvpMapPoints (point mnId per keypoint, -1 for none), or replaces a stored
+        keyframe's whole row. tie_key stands for the reference's KeyFrame* (default: mnId)."""
+        kf_id = int(kf_id)
+        ids = np.ascontiguousarray(point_ids, np.int32)
+        node = self._nodes.get(kf_id)
+        key = int(tie_key) if tie_key is not None else (node.tie_key if node else kf_id)
+        L.check(self._lib.orbfe_covis_set_keyframe(self._h, kf_id, key, len(ids), L.ptr(ids)),
+                "orbfe_covis_set_keyframe")
+        if node is None:
+            self._nodes[kf_id] = _Node(key)
+        else:
+            node.tie_key = key
+
+    def set_slots(self, kf_id: int, slots, point_ids) -> None:
+        """AddMapPoint / EraseMapPointMatch (-1) / ReplaceMapPointMatch on the given slots."""
+        s = np.ascontiguousarray(slots, np.int32)
+        p = np.ascontiguousarray(point_ids, np.int32)
+        if len(s) != len(p):
+            raise ValueError("slots / point_ids differ in length")
+        L.check(self._lib.orbfe_covis_set_slots(self._h, int(kf_id), len(s), L.ptr(s), L.ptr(p)),
+                "orbfe_covis_set_slots")
+
+    def set_points_bad(self, point_ids, bad: bool = True) -> None:
+        p = np.ascontiguousarray(point_ids, np.int32)
+        L.check(self._lib.orbfe_covis_set_points_bad(self._h, len(p), L.ptr(p), 1 if bad else 0),
+                "orbfe_covis_set_points_bad")
+
+    def erase(self, kf_id: int) -> None:
+        """Removes the keyframe's row and applies EraseConnection on every connected keyframe
+        (KeyFrame.cc:482-484, :570-584); the keyframe leaves its parent's children (:555). The spanning-tree
+        re-parenting of KeyFrame::SetBadFlag (:496-553) is out of scope: the erased keyframe's children keep naming
+        it as their parent until the caller assigns another."""
+        kf_id = int(kf_id)
+        L.check(self._lib.orbfe_covis_erase_keyframe(self._h, kf_id), "orbfe_covis_erase_keyframe")
+        node = self._nodes.pop(kf_id)
+        before = {}
+        for other in sorted(node.weights, key=lambda i: self._nodes[i].tie_key if i in self._nodes else i):
+            o = self._nodes.get(other)
+            if o is not None and kf_id in o.weights:  # EraseConnection
+                before.setdefault(other, list(o.ordered))
+                del o.weights[kf_id]
+                self._update_best_covisibles(o)
+        if node.parent is not None and node.parent in self._nodes:
+            self._nodes[node.parent].children.discard(kf_id)
+        self._mirror(before)
+
+    def clear(self) -> None:
+        L.check(self._lib.orbfe_covis_clear(self._h), "orbfe_covis_clear")
+        self._nodes.clear()
+
+    # ---- device queries -----------------------------------------------------------------------
+    def count_connections(self, kf_ids: Sequence[int], th: int = 15) -> List[SimpleNamespace]:
+        """orbfe_covis_update_connections for a batch, no side effects: per keyframe counter_ids /
+        counter_weights (KFcounter, ascending tie key), ordered_ids / ordered_weights, nmax, kf_max, unchanged."""
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        n, cap = len(ids), max(len(self) - 1, 1)
+        m = max(n, 1)
+        n_counter, n_ordered, nmax = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        kf_max, unchanged = np.zeros(m, np.int64), np.zeros(m, np.uint8)
+        c_ids, c_w = np.zeros(m * cap, np.int64), np.zeros(m * cap, np.int32)
+        o_ids, o_w = np.zeros(m * cap, np.int64), np.zeros(m * cap, np.int32)
+        r = L.covis_connections(capacity=cap, n_counter=L.ptr(n_counter), counter_ids=L.ptr(c_ids),
+                                counter_weights=L.ptr(c_w), n_ordered=L.ptr(n_ordered), ordered_ids=L.ptr(o_ids),
+                                ordered_weights=L.ptr(o_w), nmax=L.ptr(nmax), kf_max=L.ptr(kf_max),
+                                unchanged=L.ptr(unchanged))
+        L.check(self._lib.orbfe_covis_update_connections(self._h, n, L.ptr(ids), int(th), byref(r)),
+                "orbfe_covis_update_connections")
+        out = []
+        for q in range(n):
+            b, nc, no = q * cap, int(n_counter[q]), int(n_ordered[q])
+            out.append(SimpleNamespace(counter_ids=c_ids[b:b + nc].tolist(), counter_weights=c_w[b:b + nc].tolist(),
+                                       ordered_ids=o_ids[b:b + no].tolist(), ordered_weights=o_w[b:b + no].tolist(),
+                                       nmax=int(nmax[q]), kf_max=int(kf_max[q]), unchanged=bool(unchanged[q])))
+        return out
+
+    def vote(self, point_lists: Sequence[Iterable[int]]) -> List[SimpleNamespace]:
+        """The first half of Tracking::UpdateLocalKeyFrames (Tracking.cc:1257-1303) for a batch of Frames, each given
+        as its mvpMapPoints (point mnIds; -1 and bad points are skipped): per Frame kf_ids (ascending tie key:
+        mvpLocalKeyFrames' initial content), counts, max, kf_max (-1 when nothing was voted)."""
+        lists = [np.asarray(list(p), np.int32).reshape(-1) for p in point_lists]
+        nq = len(lists)
+        begin = np.zeros(nq + 1, np.int32)
+        if nq:
+            begin[1:] = np.cumsum([len(p) for p in lists])
+        pts = np.ascontiguousarray(np.concatenate(lists) if nq and begin[-1] else np.zeros(1, np.int32), np.int32)
+        cap, m = max(len(self), 1), max(nq, 1)
+        n, mx, kf_max = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int64)
+        ids, counts = np.zeros(m * cap, np.int64), np.zeros(m * cap, np.int32)
+        r = L.covis_votes(capacity=cap, n=L.ptr(n), kf_ids=L.ptr(ids), counts=L.ptr(counts), max=L.ptr(mx),
+                          kf_max=L.ptr(kf_max))
+        L.check(self._lib.orbfe_covis_vote(self._h, nq, L.ptr(begin), L.ptr(pts), byref(r)), "orbfe_covis_vote")
+        return [SimpleNamespace(kf_ids=ids[q * cap:q * cap + int(n[q])].tolist(),
+                                counts=counts[q * cap:q * cap + int(n[q])].tolist(), max=int(mx[q]),
+                                kf_max=int(kf_max[q])) for q in range(nq)]
+
+    def gather_local_map(self, local_ids: Iterable[int]) -> SimpleNamespace:
+        """orbfe_covis_local_map: point_ids (ascending), fixed_ids (ascending mnId), edge_begin, edge_kf (index into
+        sorted(local_ids) + fixed_ids), edge_slot. The capacities grow to what the gather reports."""
+        ids = np.ascontiguousarray(list(local_ids), np.int64)
+        pc, fc, ec = 4096, max(len(self), 1), 32768
+        for _ in range(2):
+            pts, fixed = np.zeros(max(pc, 1), np.int32), np.zeros(max(fc, 1), np.int64)
+            ebeg, ekf, esl = np.zeros(pc + 1, np.int32), np.zeros(max(ec, 1), np.int32), np.zeros(max(ec, 1), np.int32)
+            r = L.covis_local_map(point_capacity=pc, fixed_capacity=fc, edge_capacity=ec, point_ids=L.ptr(pts),
+                                  fixed_ids=L.ptr(fixed), edge_begin=L.ptr(ebeg), edge_kf=L.ptr(ekf),
+                                  edge_slot=L.ptr(esl))
+            st = self._lib.orbfe_covis_local_map(self._h, len(ids), L.ptr(ids), byref(r))
+            if st == L.ORBFE_ERR_CAPACITY and (r.n_points > pc or r.n_fixed > fc or r.n_edges > ec):
+                pc, fc, ec = max(pc, r.n_points), max(fc, r.n_fixed), max(ec, r.n_edges)
+                continue
+            L.check(st, "orbfe_covis_local_map")
+            break
+        else:
+            L.check(st, "orbfe_covis_local_map")
+        return SimpleNamespace(point_ids=pts[:r.n_points].copy(), fixed_ids=fixed[:r.n_fixed].copy(),
+                               edge_begin=ebeg[:r.n_points + 1].copy(), edge_kf=ekf[:r.n_edges].copy(),
+                               edge_slot=esl[:r.n_edges].copy())
+
+    # ---- the reference's side effects ----------------------------------------------------------
+    def _update_best_covisibles(self, node: _Node) -> None:
+        """KeyFrame.cc:137-157: sort the pairs (weight, KeyFrame*) ascending, push_front each."""
+        pairs = sorted((w, self._tie(i), i) for i, w in node.weights.items())
+        pairs.reverse()
+        node.ordered = [i for _, _, i in pairs]
+        node.ordered_weights = [w for w, _, _ in pairs]
+
+    def _tie(self, kf_id: int) -> int:
+        n = self._nodes.get(kf_id)
+        return n.tie_key if n is not None else kf_id
+
+    def _add_connection(self, node: _Node, other: int, weight: int) -> bool:
+        """KeyFrame.cc:122-135; True when the ordered list was rebuilt."""
+        if node.weights.get(other) == weight:
+            return False
+        node.weights[other] = weight
+        self._update_best_covisibles(node)  # the whole map, entries below th included
+        return True
+
+    def _mirror(self, before: Dict[int, List[int]]) -> None:
+        """GetBestCovisibilityKeyFrames(10) of every keyframe whose ordered list differs from `before` to the
+        KeyFrameDatabase, in the order the lists were first touched. A keyframe the database does not hold yet is
+        skipped: mirror() it after KeyFrameDatabase.add."""
+        if self._kfdb is None:
+            return
+        for kid, old in before.items():
+            node = self._nodes.get(kid)
+            if node is not None and node.ordered != old:
+                self.mirror(kid)
+
+    def mirror(self, kf_id: int) -> bool:
+        """kfdb.set_covisible(kf_id, GetBestCovisibilityKeyFrames(10)); False when the database does not hold it."""
+        try:
+            self._kfdb.set_covisible(int(kf_id), self.GetBestCovisibilityKeyFrames(kf_id, 10))
+        except L.OrbfeError as e:
+            if e.status != L.ORBFE_ERR_STATE:
+                raise
+            return False
+        return True
+
+    def _apply(self, kf_id: int, c: SimpleNamespace, before: Dict[int, List[int]]) -> None:
+        node = self._nodes[kf_id]
+        if c.unchanged:  # :339
+            return
+        # :360 / :367, in KFcounter's iteration order (ascending tie key)
+        for other, w in sorted(zip(c.ordered_ids, c.ordered_weights), key=lambda t: self._tie(t[0])):
+            o = self._nodes[other]
+            before.setdefault(other, list(o.ordered))
+            self._add_connection(o, kf_id, w)
+        before.setdefault(kf_id, list(node.ordered))
+        node.weights = dict(zip(c.counter_ids, c.counter_weights))  # :383-385
+        node.ordered = list(c.ordered_ids)
+        node.ordered_weights = list(c.ordered_weights)
+        if node.first_connection and kf_id != 0:  # :387-392
+            node.parent = node.ordered[0]
+            self._nodes[node.parent].children.add(kf_id)
+            node.first_connection = False
+
+    def update_connections(self, kf_ids, th: int = 15) -> None:
+        """KeyFrame::UpdateConnections of each keyframe: one device call for the counts, then the side effects on the
+        host in the given order."""
+        ids = [int(kf_ids)] if np.isscalar(kf_ids) else [int(i) for i in kf_ids]
+        before: Dict[int, List[int]] = {}
+        for kid, c in zip(ids, self.count_connections(ids, th)):
+            self._apply(kid, c, before)
+        self._mirror(before)
+
+    def loop_connections(self, connected_ids: Sequence[int], th: int = 15) -> Dict[int, Set[int]]:
+        """LoopClosing.cc:565-587 over mvpCurrentConnectedKFs: UpdateConnections of each, and per keyframe its new
+        connected set minus its previous ordered neighbours and minus the list itself (the LoopConnections that
+        essential_graph.py takes)."""
+        ids = [int(i) for i in connected_ids]
+        before: Dict[int, List[int]] = {}
+        out: Dict[int, Set[int]] = {}
+        for kid, c in zip(ids, self.count_connections(ids, th)):
+            previous = self.GetVectorCovisibleKeyFrames(kid)  # :571, before this keyframe's update
+            self._apply(kid, c, before)
+            out[kid] = self.GetConnectedKeyFrames(kid) - set(previous) - set(ids)
+        self._mirror(before)
+        return out
+
+    def local_map(self, kf_id: int) -> Tuple[List[int], List[int], Dict[int, Dict[int, int]]]:
+        """Optimizer.cc:456-506 for pKF: local_ids (pKF and GetVectorCovisibleKeyFrames()), fixed_ids, and point
+        mnId -> {keyframe mnId -> keypoint index} over the local points, as problem_of_local_map takes them."""
+        kf_id = int(kf_id)
+        local = [kf_id] + [i for i in self.GetVectorCovisibleKeyFrames(kf_id) if i != kf_id]
+        g = self.gather_local_map(local)
+        order = sorted(local) + g.fixed_ids.tolist()
+        obs: Dict[int, Dict[int, int]] = {}
+        for i, pid in enumerate(g.point_ids.tolist()):
+            b, e = int(g.edge_begin[i]), int(g.edge_begin[i + 1])
+            obs[pid] = {order[k]: int(s) for k, s in zip(g.edge_kf[b:e].tolist(), g.edge_slot[b:e].tolist())}
+        return local, g.fixed_ids.tolist(), obs
+
+    # ---- readers (KeyFrame.cc:159-210, :419-434) -------------------------------------------------
+    def GetConnectedKeyFrames(self, kf_id: int) -> Set[int]:
+        return set(self._nodes[int(kf_id)].weights)
+
+    def GetVectorCovisibleKeyFrames(self, kf_id: int) -> List[int]:
+        return list(self._nodes[int(kf_id)].ordered)
+
+    def GetBestCovisibilityKeyFrames(self, kf_id: int, n: int) -> List[int]:
+        return list(self._nodes[int(kf_id)].ordered[:int(n)])
+
+    def GetCovisiblesByWeight(self, kf_id: int, w: int) -> List[int]:
+        """KeyFrame.cc:185-201, its upper_bound included: when no ordered weight is below w the iterator is end()
+        and the reference returns an empty vector, not the whole list."""
+        node = self._nodes[int(kf_id)]
+        n = sum(1 for wi in node.ordered_weights if wi >= w)  # descending: a prefix
+        return [] if n == len(node.ordered) else list(node.ordered[:n])
+
+    def GetWeight(self, kf_id: int, other: int) -> int:
+        return self._nodes[int(kf_id)].weights.get(int(other), 0)
+
+    def GetParent(self, kf_id: int) -> Optional[int]:
+        return self._nodes[int(kf_id)].parent
+
+    def GetChilds(self, kf_id: int) -> Set[int]:
+        return set(self._nodes[int(kf_id)].children)
+
+    def GetOrderedWeights(self, kf_id: int) -> List[int]:
+        return list(self._nodes[int(kf_id)].ordered_weights)

@@ -1,0 +1,991 @@
+// orbfe_covis.hip -- the covisibility table on gfx950: the keyframes' mvpMapPoints rows resident on
+// the device, the observations derived from them, and the three walks of the reference over them.
+//
+// Reference: src/KeyFrame.cc:304-378 (UpdateConnections), src/Tracking.cc:1257-1303
+// (UpdateLocalKeyFrames' vote), src/Optimizer.cc:471-506 (LocalBundleAdjustment's gather).
+// include/orbfe_covis.h lists the semantics; orbfe_covis_core.h holds the host bookkeeping.
+//
+// Device layout: rows[M * S] (point id per slot, -1: none), row_n[M] (-1: free row), bad[P], and
+// three int32 arrays of P + 1 entries (a: the inverse's CSR begin; b, c: scratch of the rebuild and
+// of the local-map gather). Every per-point pass runs over n_pts = 1 + the largest id ever written.
+// An inverse entry is one uint32: bit 31 "the keyframe already appears with a lower slot", bits
+// 13-24 the keyframe's rank by mnId, bits 0-12 the slot; a segment is ascending in that word.
+// The host uploads two rank tables whenever the keyframe set changes: mnId rank per row, and tie
+// rank per mnId rank. The vote's histogram is indexed by tie rank, so its non-zero bins in index
+// order are the reference's std::map iteration, and weight << 12 | tie rank is the sort key.
+//
+// Rebuild (after any row mutation): k_covis_count (atomic count per point) -> exclusive scan
+// (k_covis_scan_local / _tops / _add, 4096 entries per workgroup, at most 4096 workgroups) ->
+// k_covis_fill (atomic cursor per point; order within a segment arbitrary) -> k_covis_canon (each
+// entry finds its place by counting the smaller words of its segment, and learns whether it is a
+// repeat of its keyframe).
+// k_covis_vote: one 1024-thread workgroup per query; a 4096-bin uint32 histogram (16 KiB) and 4096
+// sort keys (16 KiB) in LDS. Threads stride over the query's slots, walk each point's observers and
+// add with LDS atomics (integer, order-free). The bins are compacted with one block scan (counter),
+// the bins >= th go to the key array and are bitonic-sorted descending, 1024 keys per pass.
+// Local map: k_covis_lm_mark (points of the local rows) -> k_covis_lm_count (edges per marked
+// point) -> two scans -> k_covis_lm_emit (points, CSR, raw edges, seen keyframes) ->
+// k_covis_lm_order (one workgroup: local then fixed, both ascending in mnId rank) -> k_covis_lm_edges.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/orbfe.h"
+#include "../../include/orbfe_covis.h"
+#include "orbfe_covis_core.h"
+#include "orbfe_device.h"
+#include "orbfe_ktimer.h"
+
+namespace cc = orbfe_covis_core;
+
+#define COVIS_THREADS 1024
+#define COVIS_BINS 4096       // = ORBFE_COVIS_MAX_KEYFRAMES = 4 per thread
+#define COVIS_SCAN_TILE 4096  // entries per workgroup of the scan
+#define COVIS_ROW_THREADS 256
+
+static_assert(COVIS_BINS == ORBFE_COVIS_MAX_KEYFRAMES && COVIS_BINS == 4 * COVIS_THREADS, "4 bins per thread");
+static_assert(ORBFE_COVIS_MAX_SLOTS == 1 << 13, "13 slot bits in an inverse entry");
+static_assert(ORBFE_COVIS_MAX_POINT_ID <= COVIS_SCAN_TILE * 4096, "the scan's second level is one workgroup");
+
+// Exclusive scan of 4 values per thread over a 1024-thread workgroup, thread-major; returns the
+// total. s_wsum: 16 ints of LDS. Contains __syncthreads(): uniform control flow only.
+__device__ __forceinline__ int covis_block_scan4(int (&v)[4], int* s_wsum) {
+  const int lane = lane_id(), w = wave_id();
+  const int s = v[0] + v[1] + v[2] + v[3];
+  int inc = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += y;
+  }
+  if (lane == 63) s_wsum[w] = inc;
+  __syncthreads();
+  int off = 0, total = 0;
+#pragma unroll
+  for (int k = 0; k < COVIS_THREADS / 64; k++) {
+    const int x = s_wsum[k];
+    off += k < w ? x : 0;
+    total += x;
+  }
+  __syncthreads();  // s_wsum may be written again
+  int run = off + inc - s;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int x = v[j];
+    v[j] = run;
+    run += x;
+  }
+  return total;
+}
+
+// data[0..n) -> exclusive scan within each 4096-entry tile, the tile's total to tops[tile]
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_scan_local(int32_t* data, int n, int32_t* tops) {
+  __shared__ int s_wsum[COVIS_THREADS / 64];
+  const long long base = (long long)blockIdx.x * COVIS_SCAN_TILE + (int)threadIdx.x * 4;
+  int v[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) v[j] = base + j < n ? data[base + j] : 0;
+  const int total = covis_block_scan4(v, s_wsum);
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (base + j < n) data[base + j] = v[j];
+  if (threadIdx.x == 0) tops[blockIdx.x] = total;
+}
+
+// tops[0..nb) (nb <= 4096) -> exclusive scan, the grand total to *total_out
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_scan_tops(int32_t* tops, int nb, int32_t* total_out) {
+  __shared__ int s_wsum[COVIS_THREADS / 64];
+  const int base = (int)threadIdx.x * 4;
+  int v[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) v[j] = base + j < nb ? tops[base + j] : 0;
+  const int total = covis_block_scan4(v, s_wsum);
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (base + j < nb) tops[base + j] = v[j];
+  if (threadIdx.x == 0) *total_out = total;
+}
+
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_scan_add(int32_t* data, int n, const int32_t* tops) {
+  const int add = tops[blockIdx.x];
+  const long long base = (long long)blockIdx.x * COVIS_SCAN_TILE + (int)threadIdx.x * 4;
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    if (base + j < n) data[base + j] += add;
+}
+
+struct CovisTable {
+  int32_t* rows;    // [M * S]
+  int32_t* row_n;   // [M]
+  uint8_t* bad;     // [P]
+  int32_t* begin;   // [P + 1] the inverse's CSR (a)
+  uint32_t* obs;    // [obs_cap] the inverse's entries
+  int S;
+  int n_pts;        // per-point arrays are valid over 0..n_pts
+  int n_live;
+};
+
+// grid (ceil(max row / 256), rows ever used): one thread per slot
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_count(CovisTable t, int32_t* cnt) {
+  const int k = blockIdx.y, s = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (s >= t.row_n[k] || s >= t.S) return;
+  const int p = t.rows[(size_t)k * t.S + s];
+  if ((unsigned)p < (unsigned)t.n_pts) atomicAdd(&cnt[p], 1);
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_fill(CovisTable t, int32_t* cursor,
+                                                                  const int32_t* id_rank_of_row,
+                                                                  unsigned long long* tmp, long long cap) {
+  const int k = blockIdx.y, s = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (s >= t.row_n[k] || s >= t.S) return;
+  const int p = t.rows[(size_t)k * t.S + s];
+  if ((unsigned)p >= (unsigned)t.n_pts) return;
+  const long long e = (long long)t.begin[p] + atomicAdd(&cursor[p], 1);
+  if (e < cap) tmp[e] = ((unsigned long long)p << 32) | (uint32_t)((id_rank_of_row[k] << 13) | s);
+}
+
+// One thread per entry: its place in the segment is the number of smaller words there (the words
+// of a segment are distinct); it is a repeat when a smaller word names the same keyframe.
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_canon(CovisTable t, const unsigned long long* tmp,
+                                                                   long long cap) {
+  const long long e = (long long)blockIdx.x * COVIS_ROW_THREADS + threadIdx.x;
+  if (e >= cap || e >= t.begin[t.n_pts]) return;
+  const unsigned long long x = tmp[e];
+  const int p = (int)(x >> 32);
+  const uint32_t key = (uint32_t)x;
+  if ((unsigned)p >= (unsigned)t.n_pts) return;
+  const int b = t.begin[p], n = t.begin[p + 1] - b;
+  int rank = 0;
+  uint32_t dup = 0;
+  for (int j = 0; j < n; j++) {
+    const uint32_t kj = (uint32_t)tmp[b + j];
+    if (kj < key) {
+      rank++;
+      if ((kj >> 13) == (key >> 13)) dup = 1u << 31;
+    }
+  }
+  t.obs[b + rank] = key | dup;
+}
+
+// grid ceil(n / 256): rows[row * S + slots[i]] = ids[i] (the host has made the slots distinct)
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_scatter(int32_t* row, int row_len, int n,
+                                                                     const int32_t* slots, const int32_t* ids) {
+  const int i = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (i < n && (unsigned)slots[i] < (unsigned)row_len) row[slots[i]] = ids[i];
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_set_bad(uint8_t* bad, int P, int n, const int32_t* ids,
+                                                                     int flag) {
+  const int i = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (i < n && (unsigned)ids[i] < (unsigned)P) bad[ids[i]] = (uint8_t)flag;
+}
+
+struct CovisVoteArgs {
+  CovisTable t;
+  const uint16_t* tie_of_idrank;  // [n_live]
+  const int32_t* q_row;           // [n] row per query; NULL: the queries are point lists
+  const int32_t* q_self;          // [n] the query's own tie rank (excluded)
+  const int32_t* q_begin;         // [n + 1] CSR of point lists
+  const int32_t* q_points;
+  int th, want_ordered;
+  int stride;                     // entries per list in out
+  uint32_t* out;                  // per query: {n_counter, n_ordered, nmax, rank of kf_max}, counter[stride], ordered[stride]
+};
+
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_vote(CovisVoteArgs a) {
+  __shared__ uint32_t s_hist[COVIS_BINS];
+  __shared__ uint32_t s_keys[COVIS_BINS];
+  __shared__ int s_wsum[COVIS_THREADS / 64];
+  __shared__ int s_best;
+  const int tid = threadIdx.x, q = blockIdx.x;
+  for (int i = tid; i < COVIS_BINS; i += COVIS_THREADS) s_hist[i] = 0;
+  if (tid == 0) s_best = 0;
+  __syncthreads();
+  const int32_t* src;
+  int len, self;
+  if (a.q_row) {
+    const int k = a.q_row[q];
+    len = min(max(a.t.row_n[k], 0), a.t.S);
+    src = a.t.rows + (size_t)k * a.t.S;
+    self = a.q_self[q];
+  } else {
+    const int b = a.q_begin[q];
+    len = min(max(a.q_begin[q + 1] - b, 0), ORBFE_COVIS_MAX_SLOTS);
+    src = a.q_points + b;
+    self = -1;
+  }
+  for (int i = tid; i < len; i += COVIS_THREADS) {
+    const int p = src[i];
+    if ((unsigned)p >= (unsigned)a.t.n_pts) continue;  // -1: no point
+    if (a.t.bad[p]) continue;                           // isBad()
+    const int e1 = a.t.begin[p + 1];
+    for (int e = a.t.begin[p]; e < e1; e++) {
+      const uint32_t v = a.t.obs[e];
+      if (v >> 31) continue;  // the keyframe was counted at its lowest slot
+      const int r = a.tie_of_idrank[(v >> 13) & 4095u];
+      if (r != self && r < a.t.n_live) atomicAdd(&s_hist[r], 1u);
+    }
+  }
+  __syncthreads();
+  // bins 4 * tid .. + 3: counter entries in the low half of the scan word, entries >= th in the high
+  uint32_t w[4];
+  int v[4];
+  int lbest = 0;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = tid * 4 + j;
+    w[j] = s_hist[r];
+    const bool ge = a.want_ordered && w[j] > 0 && (long long)w[j] >= (long long)a.th;
+    v[j] = (w[j] > 0 ? 1 : 0) | (ge ? 1 << 16 : 0);
+    // the maximum, and among equals the lowest tie rank (the strict > while iterating ascending)
+    if (w[j] > 0) lbest = max(lbest, (int)((w[j] << 12) | (uint32_t)(COVIS_BINS - 1 - r)));
+  }
+  const int total = covis_block_scan4(v, s_wsum);
+  const int n_counter = total & 0xffff, n_ord = total >> 16;
+  uint32_t* out = a.out + (size_t)q * (4 + 2 * (size_t)a.stride);
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    if (w[j] == 0) continue;
+    const uint32_t key = (w[j] << 12) | (uint32_t)(tid * 4 + j);
+    const int pos = v[j] & 0xffff;
+    if (pos < a.stride) out[4 + pos] = key;
+    if (a.want_ordered && (long long)w[j] >= (long long)a.th) s_keys[v[j] >> 16] = key;
+  }
+  lbest = wave_max(lbest);
+  if (lane_id() == 0) atomicMax(&s_best, lbest);
+  int P2 = 64;
+  while (P2 < n_ord) P2 <<= 1;
+  __syncthreads();
+  for (int i = n_ord + tid; i < P2; i += COVIS_THREADS) s_keys[i] = 0;  // below every key (weight >= 1)
+  __syncthreads();
+  if (n_ord > 1) {  // block-uniform
+    for (int k = 2; k <= P2; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < P2; i += COVIS_THREADS) {
+          const int x = i ^ j;
+          if (x > i) {
+            const uint32_t u = s_keys[i], z = s_keys[x];
+            if ((u < z) == ((i & k) == 0)) {  // descending
+              s_keys[i] = z;
+              s_keys[x] = u;
+            }
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  for (int i = tid; i < n_ord && i < a.stride; i += COVIS_THREADS) out[4 + a.stride + i] = s_keys[i];
+  if (tid == 0) {
+    const uint32_t best = (uint32_t)s_best;
+    const uint32_t nmax = best >> 12, rmax = (uint32_t)(COVIS_BINS - 1) - (best & 4095u);
+    int n_ordered = n_ord;
+    if (a.want_ordered && n_ord == 0 && n_counter > 0) {  // KeyFrame.cc:364-368
+      n_ordered = 1;
+      if (a.stride > 0) out[4 + a.stride] = (nmax << 12) | rmax;
+    }
+    out[0] = (uint32_t)n_counter;
+    out[1] = (uint32_t)n_ordered;
+    out[2] = nmax;
+    out[3] = n_counter > 0 ? rmax : 0xffffffffu;
+  }
+}
+
+// grid (ceil(max row / 256), n_local): mark[p] = 1 for the non-bad points of the local rows
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_lm_mark(CovisTable t, const int32_t* local_rows,
+                                                                     int32_t* mark) {
+  const int k = local_rows[blockIdx.y], s = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (s >= t.row_n[k] || s >= t.S) return;
+  const int p = t.rows[(size_t)k * t.S + s];
+  if ((unsigned)p < (unsigned)t.n_pts && !t.bad[p]) mark[p] = 1;
+}
+
+// ecnt[p] = observers of a marked point, else 0
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_lm_count(CovisTable t, const int32_t* mark,
+                                                                      int32_t* ecnt) {
+  const int p = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (p >= t.n_pts) return;
+  int c = 0;
+  if (mark[p]) {
+    const int e1 = t.begin[p + 1];
+    for (int e = t.begin[p]; e < e1; e++) c += (t.obs[e] >> 31) ? 0 : 1;
+  }
+  ecnt[p] = c;
+}
+
+struct CovisEmitArgs {
+  CovisTable t;
+  const int32_t* pidx;   // [n_pts + 1] scanned marks
+  const int32_t* ebeg;   // [n_pts + 1] scanned edge counts
+  int pt_cap, edge_cap;
+  int32_t* hdr;          // {n_points, n_edges, n_fixed, 0}
+  int32_t* out_points;   // [pt_cap]
+  int32_t* out_ebeg;     // [pt_cap + 1]
+  int32_t* edge_kf;      // [edge_cap] the observer's mnId rank; k_covis_lm_edges maps it
+  int32_t* edge_slot;    // [edge_cap]
+  int32_t* seen;         // [n_live] by mnId rank
+};
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_lm_emit(CovisEmitArgs a) {
+  const int p = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (p >= a.t.n_pts) return;
+  if (p == 0) {
+    const int np = a.pidx[a.t.n_pts], ne = a.ebeg[a.t.n_pts];
+    a.hdr[0] = np;
+    a.hdr[1] = ne;
+    if (np <= a.pt_cap) a.out_ebeg[np] = ne;
+  }
+  const int i = a.pidx[p];
+  if (a.pidx[p + 1] == i) return;  // not marked
+  int e = a.ebeg[p];
+  if (i < a.pt_cap) {
+    a.out_points[i] = p;
+    a.out_ebeg[i] = e;
+  }
+  const int o1 = a.t.begin[p + 1];
+  for (int o = a.t.begin[p]; o < o1; o++) {
+    const uint32_t v = a.t.obs[o];
+    if (v >> 31) continue;
+    const int r = (int)((v >> 13) & 4095u);
+    if (r < a.t.n_live) a.seen[r] = 1;
+    if (e < a.edge_cap) {
+      a.edge_kf[e] = r;
+      a.edge_slot[e] = (int)(v & 8191u);
+    }
+    e++;
+  }
+}
+
+// One workgroup over the mnId ranks: local keyframes first, then the seen ones that are not local.
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_lm_order(int n_live, int n_local, const uint8_t* is_local,
+                                                                  const int32_t* seen, int32_t* order, int fixed_cap,
+                                                                  int32_t* out_fixed, int32_t* hdr) {
+  __shared__ int s_wsum[COVIS_THREADS / 64];
+  const int tid = threadIdx.x;
+  int v[4], kind[4];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = tid * 4 + j;
+    kind[j] = 0;
+    if (r < n_live) kind[j] = is_local[r] ? 1 : (seen[r] ? 2 : 0);
+    v[j] = kind[j] == 1 ? 1 : (kind[j] == 2 ? 1 << 16 : 0);
+  }
+  const int total = covis_block_scan4(v, s_wsum);
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    const int r = tid * 4 + j;
+    if (kind[j] == 1) {
+      order[r] = v[j] & 0xffff;
+    } else if (kind[j] == 2) {
+      const int f = v[j] >> 16;
+      order[r] = n_local + f;
+      if (f < fixed_cap) out_fixed[f] = r;
+    }
+  }
+  if (tid == 0) hdr[2] = total >> 16;
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_lm_edges(const int32_t* hdr, int edge_cap, int n_live,
+                                                                      const int32_t* order, int32_t* edge_kf) {
+  const int e = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (e >= edge_cap || e >= hdr[1]) return;
+  const int r = edge_kf[e];
+  if ((unsigned)r < (unsigned)n_live) edge_kf[e] = order[r];
+}
+
+// ------------------------------------------------------------------------------------------
+// host
+
+struct orbfe_covis {
+  int device = -1;
+  cc::Core core;
+  hipStream_t stream = nullptr;
+  int32_t* d_rows = nullptr;
+  int32_t* d_row_n = nullptr;
+  uint8_t* d_bad = nullptr;
+  int32_t* d_a = nullptr;  // [P + 1] inverse begin
+  int32_t* d_b = nullptr;  // [P + 1]
+  int32_t* d_c = nullptr;  // [P + 1]
+  int32_t* d_tops = nullptr;             // [4096]
+  int32_t* d_id_rank_of_row = nullptr;   // [M]
+  uint16_t* d_tie_of_idrank = nullptr;   // [M]
+  uint8_t* d_is_local = nullptr;         // [M]
+  int32_t* d_seen = nullptr;             // [M]
+  int32_t* d_order = nullptr;            // [M]
+  unsigned long long* d_tmp = nullptr;   // [obs_cap]
+  uint32_t* d_obs = nullptr;             // [obs_cap]
+  long long obs_cap = 0;
+  uint8_t* h_stage = nullptr;  // pinned uploads of one call
+  uint8_t* d_stage = nullptr;
+  size_t stage_cap = 0, stage_used = 0;
+  uint8_t* h_res = nullptr;    // pinned result of one call
+  uint8_t* d_res = nullptr;
+  size_t res_cap = 0;
+  std::vector<int32_t> tmp_rows, tmp_slots, tmp_ids;
+};
+
+static size_t covis_al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static int covis_fail(const char* fn, const cc::Status& st) {
+  return orbfe_set_error(st.code, (std::string(fn) + ": " + st.msg).c_str());
+}
+
+// Room for one call's uploads (`bytes` counts each piece rounded up to 256).
+static int covis_stage_reserve(orbfe_covis* h, size_t bytes) {
+  h->stage_used = 0;
+  if (bytes <= h->stage_cap) return ORBFE_OK;
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  if (h->h_stage) hipHostFree(h->h_stage);
+  if (h->d_stage) hipFree(h->d_stage);
+  h->h_stage = nullptr;
+  h->d_stage = nullptr;
+  h->stage_cap = 0;
+  const size_t cap = covis_al(bytes + bytes / 2);
+  ORBFE_HIP_CHECK(hipHostMalloc((void**)&h->h_stage, cap, hipHostMallocDefault));
+  ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_stage, cap));
+  h->stage_cap = cap;
+  return ORBFE_OK;
+}
+
+static size_t covis_stage_take(orbfe_covis* h, size_t bytes) {
+  const size_t off = h->stage_used;
+  h->stage_used += covis_al(bytes);
+  return off;
+}
+
+// Copies `bytes` of src through the pinned staging to dst (NULL: the staging's own device side);
+// returns the device address through *dev.
+static int covis_upload(orbfe_covis* h, const void* src, size_t bytes, void* dst, const void** dev) {
+  const size_t off = covis_stage_take(h, bytes);
+  if (off + bytes > h->stage_cap) return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis: staging overrun");
+  void* d = dst ? dst : (void*)(h->d_stage + off);
+  if (bytes > 0) {
+    memcpy(h->h_stage + off, src, bytes);
+    ORBFE_HIP_CHECK(hipMemcpyAsync(d, h->h_stage + off, bytes, hipMemcpyHostToDevice, h->stream));
+  }
+  if (dev) *dev = d;
+  return ORBFE_OK;
+}
+
+static int covis_res_reserve(orbfe_covis* h, size_t bytes) {
+  if (bytes <= h->res_cap) return ORBFE_OK;
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  if (h->h_res) hipHostFree(h->h_res);
+  if (h->d_res) hipFree(h->d_res);
+  h->h_res = nullptr;
+  h->d_res = nullptr;
+  h->res_cap = 0;
+  const size_t cap = covis_al(bytes + bytes / 2);
+  ORBFE_HIP_CHECK(hipHostMalloc((void**)&h->h_res, cap, hipHostMallocDefault));
+  ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_res, cap));
+  h->res_cap = cap;
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_create(int device, int max_keyframes, int max_slots, int max_point_id,
+                                  orbfe_covis** out) {
+  if (!out) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_create: bad argument");
+  *out = nullptr;
+  cc::Status cs = cc::Core::check_create(max_keyframes, max_slots, max_point_id);
+  if (cs) return covis_fail("orbfe_covis_create", cs);
+  orbfe_covis* h = new orbfe_covis();
+  h->core.init(max_keyframes, max_slots, max_point_id);
+  if (device < 0) {
+    *out = h;
+    return ORBFE_OK;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
+    delete h;
+    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_covis_create: no such HIP device");
+  }
+  h->device = device;
+  const size_t M = (size_t)max_keyframes, S = (size_t)max_slots, P = (size_t)max_point_id;
+  auto fail = [&](hipError_t e, const char* what) {
+    const int st = orbfe_set_hip_error(e, what);
+    orbfe_covis_destroy(h);
+    return st;
+  };
+#define COVIS_TRY(expr)                             \
+  do {                                              \
+    hipError_t _e = (expr);                         \
+    if (_e != hipSuccess) return fail(_e, #expr);   \
+  } while (0)
+  COVIS_TRY(hipSetDevice(device));
+  COVIS_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  COVIS_TRY(hipMalloc((void**)&h->d_rows, 4 * M * S));
+  COVIS_TRY(hipMalloc((void**)&h->d_row_n, 4 * M));
+  COVIS_TRY(hipMalloc((void**)&h->d_bad, P));
+  COVIS_TRY(hipMalloc((void**)&h->d_a, 4 * (P + 1)));
+  COVIS_TRY(hipMalloc((void**)&h->d_b, 4 * (P + 1)));
+  COVIS_TRY(hipMalloc((void**)&h->d_c, 4 * (P + 1)));
+  COVIS_TRY(hipMalloc((void**)&h->d_tops, 4 * 4096));
+  COVIS_TRY(hipMalloc((void**)&h->d_id_rank_of_row, 4 * M));
+  COVIS_TRY(hipMalloc((void**)&h->d_tie_of_idrank, 2 * M));
+  COVIS_TRY(hipMalloc((void**)&h->d_is_local, M));
+  COVIS_TRY(hipMalloc((void**)&h->d_seen, 4 * M));
+  COVIS_TRY(hipMalloc((void**)&h->d_order, 4 * M));
+  COVIS_TRY(hipMemsetAsync(h->d_row_n, 0xff, 4 * M, h->stream));
+  COVIS_TRY(hipMemsetAsync(h->d_bad, 0, P, h->stream));
+  COVIS_TRY(hipMemsetAsync(h->d_a, 0, 4 * (P + 1), h->stream));
+  COVIS_TRY(hipMemsetAsync(h->d_id_rank_of_row, 0, 4 * M, h->stream));
+  COVIS_TRY(hipMemsetAsync(h->d_tie_of_idrank, 0, 2 * M, h->stream));
+  COVIS_TRY(hipStreamSynchronize(h->stream));
+#undef COVIS_TRY
+  *out = h;
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_destroy(orbfe_covis* h) {
+  if (!h) return ORBFE_OK;
+  if (h->device >= 0) {
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    hipFree(h->d_rows);
+    hipFree(h->d_row_n);
+    hipFree(h->d_bad);
+    hipFree(h->d_a);
+    hipFree(h->d_b);
+    hipFree(h->d_c);
+    hipFree(h->d_tops);
+    hipFree(h->d_id_rank_of_row);
+    hipFree(h->d_tie_of_idrank);
+    hipFree(h->d_is_local);
+    hipFree(h->d_seen);
+    hipFree(h->d_order);
+    hipFree(h->d_tmp);
+    hipFree(h->d_obs);
+    hipFree(h->d_stage);
+    hipFree(h->d_res);
+    if (h->h_stage) hipHostFree(h->h_stage);
+    if (h->h_res) hipHostFree(h->h_res);
+    if (h->stream) hipStreamDestroy(h->stream);
+  }
+  delete h;
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_set_keyframe(orbfe_covis* h, int64_t kf_id, uint64_t tie_key, int n_slots,
+                                        const int32_t* point_ids) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_keyframe: bad argument");
+  int row = -1, top = 0;
+  cc::Status cs = h->core.prepare_keyframe(kf_id, tie_key, n_slots, point_ids, &row, &top);
+  if (cs) return covis_fail("orbfe_covis_set_keyframe", cs);
+  if (h->device >= 0) {
+    hipSetDevice(h->device);
+    int st = covis_stage_reserve(h, covis_al(4 * (size_t)n_slots) + 256);
+    if (st) return st;
+    st = covis_upload(h, point_ids, 4 * (size_t)n_slots, h->d_rows + (size_t)row * h->core.S, nullptr);
+    if (st) return st;
+    const int32_t n32 = n_slots;
+    st = covis_upload(h, &n32, 4, h->d_row_n + row, nullptr);
+    if (st) return st;
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  h->core.commit_keyframe(row, kf_id, tie_key, n_slots, top);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_set_slots(orbfe_covis* h, int64_t kf_id, int n, const int32_t* slots,
+                                     const int32_t* point_ids) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_slots: bad argument");
+  int row = -1, top = 0;
+  cc::Status cs = h->core.prepare_slots(kf_id, n, slots, point_ids, &row, &h->tmp_slots, &h->tmp_ids, &top);
+  if (cs) return covis_fail("orbfe_covis_set_slots", cs);
+  const int m = (int)h->tmp_slots.size();
+  if (h->device >= 0 && m > 0) {
+    hipSetDevice(h->device);
+    int st = covis_stage_reserve(h, 2 * covis_al(4 * (size_t)m));
+    if (st) return st;
+    const void *d_slots, *d_ids;
+    st = covis_upload(h, h->tmp_slots.data(), 4 * (size_t)m, nullptr, &d_slots);
+    if (st) return st;
+    st = covis_upload(h, h->tmp_ids.data(), 4 * (size_t)m, nullptr, &d_ids);
+    if (st) return st;
+    ORBFE_LAUNCH("k_covis_scatter", k_covis_scatter, dim3((m + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS),
+                 dim3(COVIS_ROW_THREADS), 0, h->stream, h->d_rows + (size_t)row * h->core.S, h->core.row_n[row], m,
+                 (const int32_t*)d_slots, (const int32_t*)d_ids);
+    ORBFE_HIP_CHECK(hipGetLastError());
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  h->core.commit_slots(m, top);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_erase_keyframe(orbfe_covis* h, int64_t kf_id) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_erase_keyframe: bad argument");
+  if (h->device >= 0 && h->core.slot_of.count(kf_id)) {
+    hipSetDevice(h->device);
+    ORBFE_HIP_CHECK(hipMemsetAsync(h->d_row_n + h->core.slot_of[kf_id], 0xff, 4, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  int row = -1;
+  cc::Status cs = h->core.erase(kf_id, &row);
+  if (cs) return covis_fail("orbfe_covis_erase_keyframe", cs);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_set_points_bad(orbfe_covis* h, int n, const int32_t* point_ids, int bad) {
+  if (!h || n < 0 || (n > 0 && !point_ids))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_points_bad: bad argument");
+  int top = 0;
+  cc::Status cs = h->core.check_points(n, point_ids, &top);
+  if (cs) return covis_fail("orbfe_covis_set_points_bad", cs);
+  for (int i = 0; i < n; i++)
+    if (point_ids[i] < 0) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_points_bad: a point id below 0");
+  if (h->device >= 0 && n > 0) {
+    hipSetDevice(h->device);
+    int st = covis_stage_reserve(h, covis_al(4 * (size_t)n));
+    if (st) return st;
+    const void* d_ids;
+    st = covis_upload(h, point_ids, 4 * (size_t)n, nullptr, &d_ids);
+    if (st) return st;
+    ORBFE_LAUNCH("k_covis_set_bad", k_covis_set_bad, dim3((n + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS),
+                 dim3(COVIS_ROW_THREADS), 0, h->stream, h->d_bad, h->core.P, n, (const int32_t*)d_ids, bad ? 1 : 0);
+    ORBFE_HIP_CHECK(hipGetLastError());
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_clear(orbfe_covis* h) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_clear: bad argument");
+  if (h->device >= 0) {
+    hipSetDevice(h->device);
+    ORBFE_HIP_CHECK(hipMemsetAsync(h->d_row_n, 0xff, 4 * (size_t)h->core.M, h->stream));
+    ORBFE_HIP_CHECK(hipMemsetAsync(h->d_bad, 0, (size_t)h->core.P, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  h->core.clear();
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_size(const orbfe_covis* h, int* n) {
+  if (!h || !n) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_size: bad argument");
+  *n = h->core.size();
+  return ORBFE_OK;
+}
+
+// data[0..n) -> exclusive scan in place, data[n] = the total (n >= 1)
+static void covis_scan(orbfe_covis* h, int32_t* data, int n) {
+  const int nb = (n + COVIS_SCAN_TILE - 1) / COVIS_SCAN_TILE;
+  ORBFE_LAUNCH("k_covis_scan_local", k_covis_scan_local, dim3(nb), dim3(COVIS_THREADS), 0, h->stream, data, n,
+               h->d_tops);
+  ORBFE_LAUNCH("k_covis_scan_tops", k_covis_scan_tops, dim3(1), dim3(COVIS_THREADS), 0, h->stream, h->d_tops, nb,
+               data + n);
+  if (nb > 1)
+    ORBFE_LAUNCH("k_covis_scan_add", k_covis_scan_add, dim3(nb), dim3(COVIS_THREADS), 0, h->stream, data, n,
+                 (const int32_t*)h->d_tops);
+}
+
+static CovisTable covis_table(const orbfe_covis* h) {
+  CovisTable t;
+  t.rows = h->d_rows;
+  t.row_n = h->d_row_n;
+  t.bad = h->d_bad;
+  t.begin = h->d_a;
+  t.obs = h->d_obs;
+  t.S = h->core.S;
+  t.n_pts = h->core.p_hi;
+  t.n_live = h->core.size();
+  return t;
+}
+
+static size_t covis_refresh_bytes(const orbfe_covis* h) {
+  return covis_al(4 * (size_t)h->core.M) + covis_al(2 * (size_t)h->core.M);
+}
+
+static int covis_max_row(const orbfe_covis* h) {
+  int m = 0;
+  for (int k = 0; k < h->core.hi; k++) m = std::max(m, h->core.row_n[k]);
+  return m;
+}
+
+// The rank tables and the inverse as of now, enqueued on the stream (the staging has room).
+static int covis_refresh(orbfe_covis* h) {
+  cc::Core& c = h->core;
+  if (c.ranks_dirty) {
+    c.ranks();
+    int st = covis_upload(h, c.id_rank_of_row.data(), 4 * c.id_rank_of_row.size(), h->d_id_rank_of_row, nullptr);
+    if (st) return st;
+    st = covis_upload(h, c.tie_rank_of_id_rank.data(), 2 * c.tie_rank_of_id_rank.size(), h->d_tie_of_idrank, nullptr);
+    if (st) return st;
+    c.stale = true;  // inverse entries carry mnId ranks
+  }
+  if (!c.stale) return ORBFE_OK;
+  const int n_pts = c.p_hi;
+  ORBFE_HIP_CHECK(hipMemsetAsync(h->d_a, 0, 4 * ((size_t)n_pts + 1), h->stream));
+  const int max_row = covis_max_row(h);
+  if (n_pts > 0 && c.total_slots > 0 && max_row > 0) {
+    if (c.total_slots > h->obs_cap) {
+      ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+      hipFree(h->d_tmp);
+      hipFree(h->d_obs);
+      h->d_tmp = nullptr;
+      h->d_obs = nullptr;
+      h->obs_cap = 0;
+      const long long cap = std::min<long long>(c.total_slots + c.total_slots / 2 + 1024, (long long)c.M * c.S);
+      ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_tmp, 8 * (size_t)cap));
+      ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_obs, 4 * (size_t)cap));
+      h->obs_cap = cap;
+    }
+    ORBFE_HIP_CHECK(hipMemsetAsync(h->d_c, 0, 4 * ((size_t)n_pts + 1), h->stream));
+    const CovisTable t = covis_table(h);
+    const dim3 grid((max_row + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS, c.hi);
+    ORBFE_LAUNCH("k_covis_count", k_covis_count, grid, dim3(COVIS_ROW_THREADS), 0, h->stream, t, h->d_a);
+    covis_scan(h, h->d_a, n_pts);
+    ORBFE_LAUNCH("k_covis_fill", k_covis_fill, grid, dim3(COVIS_ROW_THREADS), 0, h->stream, t, h->d_c,
+                 (const int32_t*)h->d_id_rank_of_row, h->d_tmp, h->obs_cap);
+    const long long nb = (c.total_slots + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS;
+    ORBFE_LAUNCH("k_covis_canon", k_covis_canon, dim3((unsigned)nb), dim3(COVIS_ROW_THREADS), 0, h->stream, t,
+                 (const unsigned long long*)h->d_tmp, h->obs_cap);
+    ORBFE_HIP_CHECK(hipGetLastError());
+  }
+  c.stale = false;
+  return ORBFE_OK;
+}
+
+// The vote kernel over n queries (rows, or point lists), the packed result in h_res after one
+// synchronisation: per query 4 + 2 * stride words.
+static int covis_run_votes(orbfe_covis* h, int n, const int32_t* d_rows, const int32_t* d_self,
+                           const int32_t* d_begin, const int32_t* d_points, int th, int want_ordered, int stride) {
+  const size_t bytes = 4 * (size_t)n * (4 + 2 * (size_t)stride);
+  int st = covis_res_reserve(h, bytes);
+  if (st) return st;
+  CovisVoteArgs a;
+  a.t = covis_table(h);
+  a.tie_of_idrank = h->d_tie_of_idrank;
+  a.q_row = d_rows;
+  a.q_self = d_self;
+  a.q_begin = d_begin;
+  a.q_points = d_points;
+  a.th = th;
+  a.want_ordered = want_ordered;
+  a.stride = stride;
+  a.out = reinterpret_cast<uint32_t*>(h->d_res);
+  ORBFE_LAUNCH("k_covis_vote", k_covis_vote, dim3(n), dim3(COVIS_THREADS), 0, h->stream, a);
+  ORBFE_HIP_CHECK(hipGetLastError());
+  ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, bytes, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_update_connections(orbfe_covis* h, int n, const int64_t* kf_ids, int th,
+                                              orbfe_covis_connections_t* r) {
+  if (!h || !r || r->capacity < 0 ||
+      (n > 0 && (!r->n_counter || !r->n_ordered || !r->nmax || !r->kf_max || !r->unchanged)) ||
+      (n > 0 && r->capacity > 0 &&
+       (!r->counter_ids || !r->counter_weights || !r->ordered_ids || !r->ordered_weights)))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_update_connections: bad argument");
+  cc::Status cs = h->core.rows_of(n, kf_ids, &h->tmp_rows);
+  if (cs) return covis_fail("orbfe_covis_update_connections", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "covisibility table is host-only (device < 0)");
+  if (n == 0) return ORBFE_OK;
+  hipSetDevice(h->device);
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + 2 * covis_al(4 * (size_t)n));
+  if (st) return st;
+  st = covis_refresh(h);
+  if (st) return st;
+  const cc::Core& c = h->core;
+  std::vector<int32_t> self(n);
+  for (int i = 0; i < n; i++) self[i] = c.tie_rank_of_row[h->tmp_rows[i]];
+  const void *d_rows, *d_self;
+  st = covis_upload(h, h->tmp_rows.data(), 4 * (size_t)n, nullptr, &d_rows);
+  if (st) return st;
+  st = covis_upload(h, self.data(), 4 * (size_t)n, nullptr, &d_self);
+  if (st) return st;
+  const int stride = std::max(std::min(r->capacity, c.size() - 1), 0);
+  st = covis_run_votes(h, n, (const int32_t*)d_rows, (const int32_t*)d_self, nullptr, nullptr, th, 1, stride);
+  if (st) return st;
+  const uint32_t* res = reinterpret_cast<const uint32_t*>(h->h_res);
+  const size_t per = 4 + 2 * (size_t)stride;
+  const int live = c.size();
+  for (int q = 0; q < n; q++) {
+    const uint32_t* o = res + q * per;
+    bool sane = (int)o[0] <= live && (int)o[1] <= live && (o[0] == 0 || (int)(o[3] & 4095u) < live);
+    for (int i = 0; sane && i < std::min((int)o[0], stride); i++) sane = cc::key_rank(o[4 + i]) < live;
+    for (int i = 0; sane && i < std::min((int)o[1], stride); i++) sane = cc::key_rank(o[4 + stride + i]) < live;
+    if (!sane) return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_update_connections: corrupt result");
+    if ((int)o[0] > r->capacity || (int)o[1] > r->capacity)
+      return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_covis_update_connections: result capacity below a counter");
+  }
+  for (int q = 0; q < n; q++) {
+    const uint32_t* o = res + q * per;
+    const int nc = (int)o[0], no = (int)o[1];
+    const size_t base = (size_t)q * r->capacity;
+    r->n_counter[q] = nc;
+    r->n_ordered[q] = no;
+    r->nmax[q] = (int32_t)o[2];
+    r->kf_max[q] = nc > 0 ? c.id_of[c.row_at_tie_rank[o[3] & 4095u]] : -1;
+    r->unchanged[q] = nc == 0 ? 1 : 0;
+    for (int i = 0; i < nc; i++) {
+      r->counter_ids[base + i] = c.id_of[c.row_at_tie_rank[cc::key_rank(o[4 + i])]];
+      r->counter_weights[base + i] = cc::key_weight(o[4 + i]);
+    }
+    for (int i = 0; i < no; i++) {
+      r->ordered_ids[base + i] = c.id_of[c.row_at_tie_rank[cc::key_rank(o[4 + stride + i])]];
+      r->ordered_weights[base + i] = cc::key_weight(o[4 + stride + i]);
+    }
+  }
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_vote(orbfe_covis* h, int n_queries, const int32_t* begin, const int32_t* point_ids,
+                                orbfe_covis_votes_t* r) {
+  if (!h || !r || r->capacity < 0 || (n_queries > 0 && (!r->n || !r->max || !r->kf_max)) ||
+      (n_queries > 0 && r->capacity > 0 && (!r->kf_ids || !r->counts)))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_vote: bad argument");
+  cc::Status cs = h->core.check_votes(n_queries, begin, point_ids);
+  if (cs) return covis_fail("orbfe_covis_vote", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "covisibility table is host-only (device < 0)");
+  if (n_queries == 0) return ORBFE_OK;
+  hipSetDevice(h->device);
+  const int total = begin[n_queries];
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + covis_al(4 * ((size_t)n_queries + 1)) +
+                                      covis_al(4 * (size_t)total));
+  if (st) return st;
+  st = covis_refresh(h);
+  if (st) return st;
+  const cc::Core& c = h->core;
+  const void *d_begin, *d_points;
+  st = covis_upload(h, begin, 4 * ((size_t)n_queries + 1), nullptr, &d_begin);
+  if (st) return st;
+  st = covis_upload(h, point_ids, 4 * (size_t)total, nullptr, &d_points);
+  if (st) return st;
+  const int stride = std::min(r->capacity, c.size());
+  st = covis_run_votes(h, n_queries, nullptr, nullptr, (const int32_t*)d_begin, (const int32_t*)d_points, 0, 0,
+                       stride);
+  if (st) return st;
+  const uint32_t* res = reinterpret_cast<const uint32_t*>(h->h_res);
+  const size_t per = 4 + 2 * (size_t)stride;
+  for (int q = 0; q < n_queries; q++) {
+    const int nc = (int)res[q * per];
+    bool sane = nc >= 0 && nc <= c.size() && (nc == 0 || (int)(res[q * per + 3] & 4095u) < c.size());
+    for (int i = 0; sane && i < std::min(nc, stride); i++) sane = cc::key_rank(res[q * per + 4 + i]) < c.size();
+    if (!sane) return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_vote: corrupt result");
+    if (nc > r->capacity) return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_covis_vote: result capacity below a counter");
+  }
+  for (int q = 0; q < n_queries; q++) {
+    const uint32_t* o = res + q * per;
+    const int nc = (int)o[0];
+    const size_t base = (size_t)q * r->capacity;
+    r->n[q] = nc;
+    r->max[q] = (int32_t)o[2];
+    r->kf_max[q] = nc > 0 ? c.id_of[c.row_at_tie_rank[o[3] & 4095u]] : -1;
+    for (int i = 0; i < nc; i++) {
+      r->kf_ids[base + i] = c.id_of[c.row_at_tie_rank[cc::key_rank(o[4 + i])]];
+      r->counts[base + i] = cc::key_weight(o[4 + i]);
+    }
+  }
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_local_map(orbfe_covis* h, int n_local, const int64_t* local_kf_ids,
+                                     orbfe_covis_local_map_t* r) {
+  if (!h || !r || r->point_capacity < 0 || r->fixed_capacity < 0 || r->edge_capacity < 0 || !r->edge_begin ||
+      (r->point_capacity > 0 && !r->point_ids) || (r->fixed_capacity > 0 && !r->fixed_ids) ||
+      (r->edge_capacity > 0 && (!r->edge_kf || !r->edge_slot)))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_local_map: bad argument");
+  cc::Status cs = h->core.local_rows(n_local, local_kf_ids, &h->tmp_rows);
+  if (cs) return covis_fail("orbfe_covis_local_map", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "covisibility table is host-only (device < 0)");
+  r->n_points = r->n_fixed = r->n_edges = 0;
+  r->edge_begin[0] = 0;
+  if (n_local == 0) return ORBFE_OK;
+  hipSetDevice(h->device);
+  cc::Core& c = h->core;
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + covis_al(4 * (size_t)n_local) + covis_al((size_t)c.M));
+  if (st) return st;
+  st = covis_refresh(h);
+  if (st) return st;
+  const int n_pts = c.p_hi, live = c.size();
+  const int max_row = covis_max_row(h);
+  if (n_pts == 0 || max_row == 0) {  // no row holds a point
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));  // the refresh read the staging
+    return ORBFE_OK;
+  }
+  std::vector<uint8_t> is_local(live, 0);
+  for (int i = 0; i < n_local; i++) is_local[c.id_rank_of_row[h->tmp_rows[i]]] = 1;
+  const void* d_local;
+  st = covis_upload(h, h->tmp_rows.data(), 4 * (size_t)n_local, nullptr, &d_local);
+  if (st) return st;
+  st = covis_upload(h, is_local.data(), (size_t)live, h->d_is_local, nullptr);
+  if (st) return st;
+  const int pt_cap = std::min(r->point_capacity, n_pts);
+  const int fx_cap = std::min(r->fixed_capacity, live);
+  const int ed_cap = (int)std::min<long long>(r->edge_capacity, c.total_slots);
+  // result: hdr[4] | points[pt_cap] | ebeg[pt_cap + 1] | fixed[fx_cap] | edge_kf[ed_cap] | edge_slot[ed_cap]
+  const size_t o_pts = 4, o_ebeg = o_pts + pt_cap, o_fix = o_ebeg + pt_cap + 1, o_ekf = o_fix + fx_cap,
+               o_esl = o_ekf + ed_cap, words = o_esl + ed_cap;
+  st = covis_res_reserve(h, 4 * words);
+  if (st) return st;
+  int32_t* d = reinterpret_cast<int32_t*>(h->d_res);
+  int32_t* hres = reinterpret_cast<int32_t*>(h->h_res);
+  const CovisTable t = covis_table(h);
+  ORBFE_HIP_CHECK(hipMemsetAsync(d, 0, 16, h->stream));
+  ORBFE_HIP_CHECK(hipMemsetAsync(h->d_b, 0, 4 * ((size_t)n_pts + 1), h->stream));
+  ORBFE_HIP_CHECK(hipMemsetAsync(h->d_seen, 0, 4 * (size_t)live, h->stream));
+  ORBFE_LAUNCH("k_covis_lm_mark", k_covis_lm_mark,
+               dim3((max_row + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS, n_local), dim3(COVIS_ROW_THREADS), 0,
+               h->stream, t, (const int32_t*)d_local, h->d_b);
+  const int pb = (n_pts + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS;
+  ORBFE_LAUNCH("k_covis_lm_count", k_covis_lm_count, dim3(pb), dim3(COVIS_ROW_THREADS), 0, h->stream, t,
+               (const int32_t*)h->d_b, h->d_c);
+  covis_scan(h, h->d_b, n_pts);
+  covis_scan(h, h->d_c, n_pts);
+  CovisEmitArgs ea;
+  ea.t = t;
+  ea.pidx = h->d_b;
+  ea.ebeg = h->d_c;
+  ea.pt_cap = pt_cap;
+  ea.edge_cap = ed_cap;
+  ea.hdr = d;
+  ea.out_points = d + o_pts;
+  ea.out_ebeg = d + o_ebeg;
+  ea.edge_kf = d + o_ekf;
+  ea.edge_slot = d + o_esl;
+  ea.seen = h->d_seen;
+  ORBFE_LAUNCH("k_covis_lm_emit", k_covis_lm_emit, dim3(pb), dim3(COVIS_ROW_THREADS), 0, h->stream, ea);
+  ORBFE_LAUNCH("k_covis_lm_order", k_covis_lm_order, dim3(1), dim3(COVIS_THREADS), 0, h->stream, live, n_local,
+               (const uint8_t*)h->d_is_local, (const int32_t*)h->d_seen, h->d_order, fx_cap, d + o_fix, d);
+  if (ed_cap > 0)
+    ORBFE_LAUNCH("k_covis_lm_edges", k_covis_lm_edges, dim3((ed_cap + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS),
+                 dim3(COVIS_ROW_THREADS), 0, h->stream, (const int32_t*)d, ed_cap, live, (const int32_t*)h->d_order,
+                 d + o_ekf);
+  ORBFE_HIP_CHECK(hipGetLastError());
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres, d, 16, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  const int np = hres[0], ne = hres[1], nf = hres[2];
+  if (np < 0 || np > n_pts || ne < 0 || ne > c.total_slots || nf < 0 || nf > live)
+    return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_local_map: corrupt result");
+  if (np > r->point_capacity || nf > r->fixed_capacity || ne > r->edge_capacity) {
+    r->n_points = np;
+    r->n_fixed = nf;
+    r->n_edges = ne;
+    return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_covis_local_map: a result capacity below what the gather found");
+  }
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres + o_pts, d + o_pts, 4 * (size_t)np, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres + o_ebeg, d + o_ebeg, 4 * ((size_t)np + 1), hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres + o_fix, d + o_fix, 4 * (size_t)nf, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres + o_ekf, d + o_ekf, 4 * (size_t)ne, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres + o_esl, d + o_esl, 4 * (size_t)ne, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  r->n_points = np;
+  r->n_fixed = nf;
+  r->n_edges = ne;
+  if (np > 0) memcpy(r->point_ids, hres + o_pts, 4 * (size_t)np);
+  memcpy(r->edge_begin, hres + o_ebeg, 4 * ((size_t)np + 1));
+  for (int i = 0; i < nf; i++) {
+    const int rank = hres[o_fix + i];
+    if (rank < 0 || rank >= live) return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_local_map: corrupt result");
+    r->fixed_ids[i] = c.id_of[c.row_at_id_rank[rank]];
+  }
+  if (ne > 0) {
+    memcpy(r->edge_kf, hres + o_ekf, 4 * (size_t)ne);
+    memcpy(r->edge_slot, hres + o_esl, 4 * (size_t)ne);
+  }
+  return ORBFE_OK;
+}
