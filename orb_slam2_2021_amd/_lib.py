@@ -1,7 +1,8 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h).
+orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h,
+orbfe_mapcorr.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -283,6 +284,45 @@ GBA_FLAG_LARGE_STEP, GBA_FLAG_NONFINITE = 1, 2
 GBA_STOP_ALL, GBA_STOP_TERMINATE, GBA_STOP_NBAD, GBA_STOP_NO_EDGE, GBA_STOP_FLAG = 0, 1, 2, 3, 4
 
 
+class mapcorr_points(Structure):  # orbfe_mapcorr.h
+    _fields_ = [("n_points", c_int), ("n_obs", c_int), ("n_levels", c_int), ("scale_factors", c_void_p),
+                ("xw", c_void_p), ("bad", c_void_p), ("obs_begin", c_void_p), ("obs_kf", c_void_p),
+                ("ref_kf", c_void_p), ("ref_level", c_void_p)]
+
+
+class mapcorr_normals(Structure):
+    _fields_ = [("normal", c_void_p), ("max_dist", c_void_p), ("min_dist", c_void_p), ("updated", c_void_p)]
+
+
+class mapcorr_normals_problem(Structure):
+    _fields_ = [("n_kf", c_int), ("ow", c_void_p), ("points", mapcorr_points)]
+
+
+class mapcorr_loop_problem(Structure):
+    _fields_ = [("n_kf", c_int), ("tcw", c_void_p), ("n_connected", c_int), ("connected_kf", c_void_p), ("cur", c_int),
+                ("scw", c_void_p), ("n_slots", c_int), ("row_begin", c_void_p), ("row_point", c_void_p),
+                ("points", mapcorr_points)]
+
+
+class mapcorr_loop_result(Structure):
+    _fields_ = [("noncorrected_sim3", c_void_p), ("corrected_sim3", c_void_p), ("tcw_out", c_void_p),
+                ("xw_out", c_void_p), ("corrected_by", c_void_p), ("normals", mapcorr_normals)]
+
+
+class mapcorr_gba_problem(Structure):
+    _fields_ = [("n_kf", c_int), ("tcw", c_void_p), ("tcw_gba", c_void_p), ("optimised", c_void_p),
+                ("parent", c_void_p), ("n_points", c_int), ("xw", c_void_p), ("bad", c_void_p),
+                ("pt_optimised", c_void_p), ("xw_gba", c_void_p), ("ref_kf", c_void_p)]
+
+
+class mapcorr_gba_result(Structure):
+    _fields_ = [("tcw_out", c_void_p), ("propagated", c_void_p), ("xw_out", c_void_p), ("pt_changed", c_void_p),
+                ("levels", c_int)]
+
+
+MAPCORR_MAX_KF, MAPCORR_MAX_POINTS, MAPCORR_MAX_EDGES, MAPCORR_MAX_LEVELS = 8192, 1048576, 16777216, 64  # orbfe_mapcorr.h
+
+
 class essgraph_problem(Structure):  # orbfe_essgraph.h
     _fields_ = [("n_vertices", c_int), ("tcw", c_void_p), ("fixed_vertex", c_int), ("fix_scale", c_int),
                 ("n_corrected", c_int), ("corrected_idx", c_void_p), ("corrected_sim3", c_void_p),
@@ -539,6 +579,12 @@ _SIGNATURES = {
     "orbfe_gba_destroy": (c_int, [c_void_p]),
     "orbfe_gba_solve": (c_int, [c_void_p, c_void_p, c_void_p]),
     "orbfe_gba_envelope": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    # orbfe_mapcorr.h
+    "orbfe_mapcorr_create": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
+    "orbfe_mapcorr_destroy": (c_int, [c_void_p]),
+    "orbfe_mapcorr_update_normal_depth": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "orbfe_mapcorr_correct_loop": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "orbfe_mapcorr_apply_gba": (c_int, [c_void_p, c_void_p, c_void_p]),
     # orbfe_essgraph.h
     "orbfe_essgraph_create": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_essgraph_destroy": (c_int, [c_void_p]),
