@@ -11,9 +11,10 @@
 //   k_eg_assemble      64 lanes per block: a diagonal block with b_s, or an off-diagonal block that has
 //                      edges, summed in ascending edge index
 //   k_eg_lambda        per diagonal scalar: + lambda on the copy
-//   k_eg_factor        one workgroup: the right-looking block LDL^T over the envelope (per pivot block:
+//   k_eg_factor        one workgroup: orbfe_env_core.h's block LDL^T over the envelope (per pivot block:
 //                      its 7 x 7 factorisation, the scaled column below, the trailing updates), then the
-//                      forward and the backward substitution
+//                      forward and the backward substitution; the routines orbfe_gba.hip runs as
+//                      k_gba_pivot / trailing / subst
 //   k_eg_update        per vertex: oplus into the trial estimate
 //   k_eg_chi           per edge: the error at the trial estimates
 //   k_eg_reduce        one wavefront: the total chi2 and computeScale by the 64-lane rule
@@ -84,126 +85,52 @@ __global__ __launch_bounds__(EG_BLOCK) void k_eg_lambda(EgWs w, double lambda) {
   if (t < 7 * w.ns) eg_add_lambda(w, t / 7, t % 7, lambda);
 }
 
-// The block order of the scalar rule: an entry takes its updates pivot block by pivot block, inside a
-// block p = 0 .. 6, so in ascending scalar pivot index; it is divided by d_j when column j's block is the
-// pivot. The substitutions visit the blocks in the same ascending (forward) and descending (backward)
-// order. y holds the right-hand side throughout; x is written only after a successful factorisation.
+// orbfe_env_core.h's factorisation and substitutions (env_*<7>) by one workgroup: per pivot block its
+// diagonal block by thread 0, the column below it one scalar row per thread, the trailing updates one
+// scalar per thread; then the forward and the backward substitution, block by block. y holds the
+// right-hand side throughout; x is written only after a successful factorisation.
 __global__ __launch_bounds__(EG_FACTOR_THREADS) void k_eg_factor(EgWs w) {
   __shared__ double sD[49];
-  __shared__ double sd[7];
+  __shared__ double sd[7];  // the pivot block's d: the bits of e.d, read by every thread of the two loops below
   __shared__ int s_fail;
-  const int tid = threadIdx.x, nt = EG_FACTOR_THREADS, ns = w.ns;
-  if (tid == 0) s_fail = 0;
-  __syncthreads();
+  const EnvWs e = eg_env(w);
+  const int tid = threadIdx.x, nt = EG_FACTOR_THREADS, ns = e.ns, n = 7 * ns;
   for (int b = 0; b < ns; b++) {
-    double* diag = w.L + ((size_t)w.row_off[b + 1] - 1) * 49;
     if (tid == 0) {
-      for (int r = 0; r < 7; r++)
-        for (int c = 0; c <= r; c++) sD[7 * r + c] = diag[7 * r + c];
-      for (int p = 0; p < 7 && !s_fail; p++) {
-        const double dp = sD[8 * p];
-        if (!po_finite(dp)) s_fail = 2;
-        else if (dp == 0.0) s_fail = 1;
-        if (s_fail) break;
-        sd[p] = dp;
-        w.d[7 * (size_t)b + p] = dp;
-        for (int r = p + 1; r < 7; r++) sD[7 * r + p] = sD[7 * r + p] / dp;
-        for (int r = p + 1; r < 7; r++) {
-          const double m = sD[7 * r + p] * dp;
-          for (int c = p + 1; c <= r; c++) sD[7 * r + c] = sD[7 * r + c] - m * sD[7 * c + p];
-        }
-      }
-      if (!s_fail)
-        for (int r = 0; r < 7; r++)
-          for (int c = 0; c < r; c++) diag[7 * r + c] = sD[7 * r + c];
+      s_fail = env_pivot_diag<7>(e, b, sD);
+      for (int p = 0; p < 7; p++) sd[p] = sD[8 * p];
     }
     __syncthreads();
     if (s_fail) {  // the same value in every thread
       if (tid == 0) lm_fail(w.rec, s_fail == 2 ? LM_FLAG_NONFINITE : 0u);
       return;
     }
-    const int c0 = w.col_begin[b], nr = w.col_begin[b + 1] - c0;
-    for (int t = tid; t < nr * 7; t += nt) {  // the column below: one scalar row per thread
-      const int s = w.col_row[c0 + t / 7];
-      double* row = w.L + ((size_t)w.row_off[s] + (b - w.row_first[s])) * 49 + 7 * (t % 7);
-      double v[7];
-#pragma unroll
-      for (int c = 0; c < 7; c++) v[c] = row[c];
-#pragma unroll
-      for (int c = 0; c < 7; c++) {
-        double a = v[c];
-#pragma unroll
-        for (int p = 0; p < 7; p++)
-          if (p < c) a = a - (v[p] * sd[p]) * sD[7 * c + p];
-        v[c] = a / sd[c];
-      }
-#pragma unroll
-      for (int c = 0; c < 7; c++) row[c] = v[c];
-    }
+    const int rows = 7 * (e.col_begin[b + 1] - e.col_begin[b]);
+    for (int t = tid; t < rows; t += nt) env_scale_row<7>(e, b, t, sD, sd);
     __syncthreads();
-    const long long items = (long long)nr * nr * 49;  // the trailing blocks (a, bb), bb <= a, both rows of the column
-    for (long long t = tid; t < items; t += nt) {
-      const int a = (int)(t / (nr * 49)), rem = (int)(t % (nr * 49)), bb = rem / 49, idx = rem % 49, r = idx / 7, c = idx % 7;
-      if (bb > a || (bb == a && c > r)) continue;
-      const int sa = w.col_row[c0 + a], sb = w.col_row[c0 + bb];
-      const double* La = w.L + ((size_t)w.row_off[sa] + (b - w.row_first[sa])) * 49 + 7 * r;
-      const double* Lb = w.L + ((size_t)w.row_off[sb] + (b - w.row_first[sb])) * 49 + 7 * c;
-      double* dst = w.L + ((size_t)w.row_off[sa] + (sb - w.row_first[sa])) * 49 + idx;
-      double x = *dst;
-#pragma unroll
-      for (int p = 0; p < 7; p++) x = x - (La[p] * sd[p]) * Lb[p];
-      *dst = x;
-    }
+    const long long items = env_trailing_items(e, b, 7);
+    for (long long t = tid; t < items; t += nt) env_trailing_item<7>(e, b, t, sd);
     __syncthreads();
   }
-  const int n = 7 * ns;
-  for (int i = tid; i < n; i += nt) w.y[i] = w.b[i];
+  for (int i = tid; i < n; i += nt) e.y[i] = w.b[i];
   __syncthreads();
-  for (int b = 0; b < ns; b++) {  // forward: y_i -= L_ik y_k, k ascending
-    const double* diag = w.L + ((size_t)w.row_off[b + 1] - 1) * 49;
-    double* yb = w.y + 7 * (size_t)b;
-    if (tid == 0)
-      for (int r = 1; r < 7; r++) {
-        double v = yb[r];
-        for (int p = 0; p < r; p++) v = v - diag[7 * r + p] * yb[p];
-        yb[r] = v;
-      }
+  for (int b = 0; b < ns; b++) {
+    if (tid == 0) env_forward_diag<7>(e, b);
     __syncthreads();
-    const int c0 = w.col_begin[b], nr = w.col_begin[b + 1] - c0;
-    for (int t = tid; t < nr * 7; t += nt) {
-      const int s = w.col_row[c0 + t / 7], r = t % 7;
-      const double* row = w.L + ((size_t)w.row_off[s] + (b - w.row_first[s])) * 49 + 7 * r;
-      double v = w.y[7 * (size_t)s + r];
-#pragma unroll
-      for (int p = 0; p < 7; p++) v = v - row[p] * yb[p];
-      w.y[7 * (size_t)s + r] = v;
-    }
+    const int rows = 7 * (e.col_begin[b + 1] - e.col_begin[b]);
+    for (int t = tid; t < rows; t += nt) env_forward_row<7>(e, b, t);
     __syncthreads();
   }
-  for (int i = tid; i < n; i += nt) w.y[i] = w.y[i] / w.d[i];
+  for (int i = tid; i < n; i += nt) e.y[i] = e.y[i] / e.d[i];
   __syncthreads();
-  for (int s = ns - 1; s >= 0; s--) {  // backward: x_i -= L_ki x_k, k descending
-    const double* rowblk = w.L + (size_t)w.row_off[s] * 49;
-    const int nb = s - w.row_first[s];
-    double* ys = w.y + 7 * (size_t)s;
-    if (tid == 0)
-      for (int r = 6; r >= 1; r--) {
-        const double xr = ys[r];
-        for (int c = 0; c < r; c++) ys[c] = ys[c] - rowblk[(size_t)nb * 49 + 7 * r + c] * xr;
-      }
+  for (int s = ns - 1; s >= 0; s--) {
+    if (tid == 0) env_backward_diag<7>(e, s);
     __syncthreads();
-    for (int t = tid; t < nb * 7; t += nt) {
-      const int cb = t / 7, cc = t % 7;
-      const double* blk = rowblk + (size_t)cb * 49;
-      double* dst = w.y + 7 * (size_t)(w.row_first[s] + cb) + cc;
-      double v = *dst;
-#pragma unroll
-      for (int r = 6; r >= 0; r--) v = v - blk[7 * r + cc] * ys[r];
-      *dst = v;
-    }
+    const int cols = 7 * (s - e.row_first[s]);
+    for (int t = tid; t < cols; t += nt) env_backward_col<7>(e, s, t);
     __syncthreads();
   }
-  for (int i = tid; i < n; i += nt) w.x[i] = w.y[i];
+  for (int i = tid; i < n; i += nt) w.x[i] = e.y[i];
 }
 
 __global__ __launch_bounds__(EG_BLOCK) void k_eg_update(EgWs w) {

@@ -16,12 +16,13 @@
 //   per block    an off-diagonal block runs over its edges (duplicates allowed) in ascending edge index;
 //   totals       edge e (chi2) and slot s (computeScale) belong to lane e % 64 / s % 64; a lane adds in
 //                ascending index from +0.0; the lanes are combined by s[l] += s[l + stride], 32 .. 1.
-// The linear solve is an unpivoted LDL^T in natural order over the block envelope: entry (i, j) is
-// v = A_ij; v = v - (L_ik d_k) L_jk for k ascending inside both rows' envelopes; L_ij = v / d_j. Every
-// entry's updates come in ascending pivot index, so any mapping of entries to threads gives the same bits.
+// The linear solve is orbfe_env_core.h's unpivoted LDL^T in natural order over the 7x7 block envelope
+// (env_*<7>): entry (i, j) is v = A_ij; v = v - (L_ik d_k) L_jk for k ascending inside both rows'
+// envelopes; L_ij = v / d_j.
 // Every loop is capped by a count the host has checked; every index read from memory was checked by the
 // host (orbfe_essgraph_solve) or built by it (eg_plan).
 #pragma once
+#include "orbfe_env_core.h"
 #include "orbfe_lm_core.h"
 #include "orbfe_optsim3_core.h"  // Sim3: OsSim3, os_sim3_*, os_oplus, os_exp, po_sincos, the quaternion rules
 
@@ -415,11 +416,9 @@ PO_HD inline void eg_add_lambda(const EgWs& w, int s, int r, double lambda) {
   w.L[at] = w.H[at] + lambda;
 }
 
-// ---- the envelope LDL^T by scalars (the host's order; the kernel's block order gives the same bits) -----
-PO_HD inline size_t eg_at(const EgWs& w, int i, int j) {  // i >= j, column block inside row i's envelope
-  const int si = i / 7, sj = j / 7;
-  return ((size_t)w.row_off[si] + (sj - w.row_first[si])) * 49 + 7 * (i % 7) + (j % 7);
-}
+// The envelope of the system as orbfe_env_core.h reads it: L is factored in place, y takes b before the
+// forward substitution
+PO_HD inline EnvWs eg_env(const EgWs& w) { return {w.ns, w.row_first, w.row_off, w.col_begin, w.col_row, w.L, w.d, w.y}; }
 
 // ---- update, chi2, computeScale -----------------------------------------------------------------------
 // SparseOptimizer::update into the trial estimate: oplus for a vertex in the system, a copy otherwise.
@@ -523,14 +522,14 @@ struct EgOut {
   EgTrace trace;
 };
 
-struct EgPlan {
-  int nv = 0, ne = 0, ns = 0, nob = 0, np = 0;
-  long long nblk = 0;
-  std::vector<int> corr_of_v, nonc_of_v, slot_of_v, v_of_slot, ve_begin, ve_edge, row_first, row_off, ob_begin, ob_pos, ob_edge,
-      col_begin, col_row;
+struct EgPlan : EnvPlan {  // ns, nblk, row_first, row_off, col_begin, col_row
+  int nv = 0, ne = 0, nob = 0, np = 0;
+  std::vector<int> corr_of_v, nonc_of_v, slot_of_v, v_of_slot, ve_begin, ve_edge, ob_begin, ob_pos, ob_edge;
 };
 
-// The slots and the envelope: one pass over the edges. The indices of `in` are checked by the caller.
+// The slots and the envelope: one pass over the edges, then env_plan_structure stopped at the count (a
+// capacity of 0 blocks): the caller holds nblk against its own capacity before eg_plan_rest builds the
+// rest. The indices of `in` are checked by the caller.
 inline void eg_plan_envelope(const EgIn& in, EgPlan* P) {
   P->nv = in.nv, P->ne = in.ne, P->np = in.np;
   std::vector<uint8_t> used(in.nv, 0);
@@ -547,18 +546,16 @@ inline void eg_plan_envelope(const EgIn& in, EgPlan* P) {
     const int hi = a > b ? a : b, lo = a > b ? b : a;
     if (lo < P->row_first[hi]) P->row_first[hi] = lo;
   }
-  P->nblk = 0;
-  for (int s = 0; s < P->ns; s++) P->nblk += s - P->row_first[s] + 1;
+  env_plan_structure(P, 0);
 }
 
 // The rest of the structure; nblk fits the handle (checked by the caller between the two)
 inline void eg_plan_rest(const EgIn& in, EgPlan* P) {
   const int ns = P->ns;
+  env_plan_structure(P, P->nblk);
   P->corr_of_v.assign(in.nv, -1), P->nonc_of_v.assign(in.nv, -1);
   for (int k = 0; k < in.ncorr; k++) P->corr_of_v[in.corr_idx[k]] = k;
   for (int k = 0; k < in.nnonc; k++) P->nonc_of_v[in.nonc_idx[k]] = k;
-  P->row_off.assign(ns + 1, 0);
-  for (int s = 0; s < ns; s++) P->row_off[s + 1] = P->row_off[s] + (s - P->row_first[s] + 1);
   P->ve_begin.assign(ns + 1, 0);
   for (int e = 0; e < in.ne; e++) {
     const int a = P->slot_of_v[in.e_i[e]], b = P->slot_of_v[in.e_j[e]];
@@ -588,14 +585,6 @@ inline void eg_plan_rest(const EgIn& in, EgPlan* P) {
   }
   if (!obs.empty()) P->ob_begin.push_back((int)obs.size());
   P->nob = (int)P->ob_pos.size();
-  P->col_begin.assign(ns + 1, 0);
-  for (int s = 0; s < ns; s++)
-    for (int c = P->row_first[s]; c < s; c++) P->col_begin[c + 1]++;
-  for (int s = 0; s < ns; s++) P->col_begin[s + 1] += P->col_begin[s];
-  P->col_row.assign(P->col_begin[ns], 0);
-  std::vector<int> cat(P->col_begin.begin(), P->col_begin.end() - 1);
-  for (int s = 0; s < ns; s++)
-    for (int c = P->row_first[s]; c < s; c++) P->col_row[cat[c]++] = s;
 }
 
 // Optimizer.cc:784-1048 after the caller's gather: SparseOptimizer::optimize(20) by orbfe_lm_core.h's
@@ -683,31 +672,32 @@ struct EgHostBackend {
     w.L = L.data();
     for (int s = 0; s < w.ns; s++)
       for (int r = 0; r < 7; r++) eg_add_lambda(w, s, r, lambda);
-    // row i: its entries left to right; a d_i that is 0, or not finite (deviation), fails the trial
-    for (int i = 0; i < n && !rec.fail; i++) {
-      const int ci = 7 * w.row_first[i / 7];
-      for (int j = ci; j <= i; j++) {
-        const int cj = 7 * w.row_first[j / 7];
-        double v = w.L[eg_at(w, i, j)];
-        for (int k = ci > cj ? ci : cj; k < j; k++) v = v - (w.L[eg_at(w, i, k)] * w.d[k]) * w.L[eg_at(w, j, k)];
-        if (j < i) {
-          w.L[eg_at(w, i, j)] = v / w.d[j];
-        } else {
-          w.d[i] = v;
-          if (!po_finite(v)) lm_fail(w.rec, LM_FLAG_NONFINITE);
-          else if (v == 0.0) lm_fail(w.rec, 0);
-        }
+    // a d_j that is 0, or not finite (deviation), fails the trial
+    const EnvWs env = eg_env(w);
+    for (int b = 0; b < w.ns; b++) {
+      double sD[49];
+      const int bad = env_pivot_diag<7>(env, b, sD);
+      if (bad) {
+        lm_fail(w.rec, bad == 2 ? LM_FLAG_NONFINITE : 0u);
+        break;
       }
+      const int nr = env.col_begin[b + 1] - env.col_begin[b];
+      for (int t = 0; t < 7 * nr; t++) env_scale_row<7>(env, b, t, sD, env.d + 7 * b);
+      const long long items = env_trailing_items(env, b, 7);
+      for (long long t = 0; t < items; t++) env_trailing_item<7>(env, b, t, env.d + 7 * b);
     }
     if (!rec.fail) {
-      for (int i = 0; i < n; i++) {
-        double v = w.b[i];
-        for (int k = 7 * w.row_first[i / 7]; k < i; k++) v = v - w.L[eg_at(w, i, k)] * w.y[k];
-        w.y[i] = v;
+      for (int i = 0; i < n; i++) w.y[i] = w.b[i];
+      for (int b = 0; b < w.ns; b++) {
+        env_forward_diag<7>(env, b);
+        const int nr = env.col_begin[b + 1] - env.col_begin[b];
+        for (int t = 0; t < 7 * nr; t++) env_forward_row<7>(env, b, t);
       }
       for (int i = 0; i < n; i++) w.y[i] = w.y[i] / w.d[i];
-      for (int k = n - 1; k >= 0; k--)
-        for (int i = 7 * w.row_first[k / 7]; i < k; i++) w.y[i] = w.y[i] - w.L[eg_at(w, k, i)] * w.y[k];
+      for (int s = w.ns - 1; s >= 0; s--) {
+        env_backward_diag<7>(env, s);
+        for (int t = 0; t < 7 * (s - env.row_first[s]); t++) env_backward_col<7>(env, s, t);
+      }
       for (int i = 0; i < n; i++) w.x[i] = w.y[i];
     }
     for (int v = 0; v < w.nv; v++) eg_update_vertex(w, v);

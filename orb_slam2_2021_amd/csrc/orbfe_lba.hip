@@ -3,16 +3,18 @@
 //
 // The Levenberg control flow (lba_run of orbfe_lba_core.h over lm_host_optimize of orbfe_lm_core.h) runs on
 // the host and reads one LmRec per linearisation and per trial; the stages are kernels on the handle's
-// one stream, each a thread- or lane-per-element call of the core header's functions:
-//   k_lba_edge      per active edge: error, robust weight and (linearisation) Jacobians and the edge's
+// one stream, each a thread- or lane-per-element call of the core header's functions. Those marked *
+// are orbfe_ba_device.h's k_ba_* kernels, the one set this file and orbfe_gba.hip both launch, under this
+// file's labels for the kernel timer:
+//   k_lba_edge*     per active edge: error, robust weight and (linearisation) Jacobians and the edge's
 //                   own Hll, bl, Hpl, Hpp, bp products
-//   k_lba_point     per point: Hll, bl, chi2 share over its edges in order
-//   k_lba_pose      one wavefront per free keyframe: Hpp(i,i), bp_i by the 64-lane rule
-//   k_lba_dinv      per point: Dinv = (Hll + lambda I)^-1, db
+//   k_lba_point*    per point: Hll, bl, chi2 share over its edges in order
+//   k_lba_pose*     one wavefront per free keyframe: Hpp(i,i), bp_i by the 64-lane rule
+//   k_lba_dinv*     per point: Dinv = (Hll + lambda I)^-1, db
 //   k_lba_schur     one wavefront per (s1 <= s2): the Schur block and, on the diagonal, bschur
 //   k_lba_ldlt      one workgroup: the dense LDL^T by columns in global memory and the two solves
-//   k_lba_update    per point: back-substitution and the trial point; per keyframe: exp(x) * T
-//   k_lba_reduce    one wavefront: the total chi2 with computeLambdaInit's maximum or computeScale
+//   k_lba_update*   per point: back-substitution and the trial point; per keyframe: exp(x) * T
+//   k_lba_reduce*   one wavefront: the total chi2 with computeLambdaInit's maximum or computeScale
 //   k_lba_classify  per edge: chi2 > th || !isDepthPositive
 // No kernel waits on another: the stream orders them. Every index a kernel reads was checked by
 // orbfe_lba_solve or built by lba_plan / lba_active; every loop runs to a count among those.
@@ -23,9 +25,7 @@
 #include <vector>
 
 #include "../../include/orbfe_lba.h"
-#include "orbfe_device.h"
-#include "orbfe_ktimer.h"
-#include "orbfe_lba_core.h"
+#include "orbfe_ba_device.h"
 
 static_assert(LM_FLAG_LARGE_STEP == ORBFE_LBA_FLAG_LARGE_STEP && LM_FLAG_NONFINITE == ORBFE_LBA_FLAG_NONFINITE, "flag values");
 static_assert(LM_STOP_ALL == ORBFE_LBA_STOP_ALL && LM_STOP_TERMINATE == ORBFE_LBA_STOP_TERMINATE &&
@@ -35,43 +35,9 @@ static_assert(LM_STOP_ALL == ORBFE_LBA_STOP_ALL && LM_STOP_TERMINATE == ORBFE_LB
 static_assert(sizeof(LbaRound) == sizeof(orbfe_lba_round_t), "trace layout");
 static_assert(LBA_MAX_FREE == ORBFE_LBA_MAX_FREE_KF, "free keyframe cap");
 
-#define LBA_BLOCK 128
 #define LBA_LDLT_THREADS 256
 #define LBA_LDLT_ROWS 3  // rows of one column a thread owns
 static_assert(6 * LBA_MAX_FREE <= LBA_LDLT_ROWS * LBA_LDLT_THREADS, "k_lba_ldlt covers a column in one pass");
-
-template <bool FULL>
-__global__ __launch_bounds__(LBA_BLOCK) void k_lba_edge(LbaWs w, int trial) {
-  const int e = blockIdx.x * LBA_BLOCK + threadIdx.x;
-  if (e < w.ne) lba_edge<FULL>(w, e, trial != 0);
-}
-
-template <bool FULL>
-__global__ __launch_bounds__(LBA_BLOCK) void k_lba_point(LbaWs w) {
-  const int p = blockIdx.x * LBA_BLOCK + threadIdx.x;
-  if (p < w.np) lba_point_sum<FULL>(w, p);
-}
-
-// the tree: lane 0 ends with s[0] of the host's s[l] += s[l + stride]
-__device__ inline double lba_tree(double v) {
-#pragma unroll
-  for (int stride = LBA_LANES / 2; stride >= 1; stride >>= 1) v = v + __shfl_down(v, stride);
-  return v;
-}
-
-__global__ __launch_bounds__(LBA_LANES) void k_lba_pose(LbaWs w) {
-  const int f = w.free_of_slot[blockIdx.x];
-  double acc[27];
-  lba_pose_lane(w, f, threadIdx.x, acc);
-#pragma unroll
-  for (int k = 0; k < 27; k++) acc[k] = lba_tree(acc[k]);
-  if (threadIdx.x == 0) lba_pose_finish(w, f, acc);
-}
-
-__global__ __launch_bounds__(LBA_BLOCK) void k_lba_dinv(LbaWs w, double lambda) {
-  const int p = blockIdx.x * LBA_BLOCK + threadIdx.x;
-  if (p < w.np) lba_point_dinv(w, p, lambda);
-}
 
 __global__ __launch_bounds__(LBA_LANES) void k_lba_schur(LbaWs w, double lambda) {
   const int s1 = blockIdx.y, s2 = blockIdx.x;
@@ -79,7 +45,7 @@ __global__ __launch_bounds__(LBA_LANES) void k_lba_schur(LbaWs w, double lambda)
   double acc[42];
   lba_schur_lane(w, w.free_of_slot[s1], w.free_of_slot[s2], threadIdx.x, acc);
 #pragma unroll
-  for (int k = 0; k < 42; k++) acc[k] = lba_tree(acc[k]);
+  for (int k = 0; k < 42; k++) acc[k] = ba_tree(acc[k]);
   if (threadIdx.x == 0) lba_schur_finish(w, s1, s2, lambda, acc);
 }
 
@@ -138,36 +104,8 @@ __global__ __launch_bounds__(LBA_LDLT_THREADS) void k_lba_ldlt(LbaWs w) {
   for (int i = tid; i < n; i += LBA_LDLT_THREADS) w.xp[i] = sy[i];
 }
 
-__global__ __launch_bounds__(LBA_BLOCK) void k_lba_update(LbaWs w) {
-  const int i = blockIdx.x * LBA_BLOCK + threadIdx.x;
-  if (i < w.np) {
-    if (!w.rec->fail) lba_point_backsub(w, i);  // after a failed solve x keeps its last values
-    lba_update_point(w, i);
-  } else if (i - w.np < w.nk) {
-    lba_update_kf(w, i - w.np);
-  }
-}
-
-__global__ __launch_bounds__(LBA_LANES) void k_lba_reduce(LbaWs w, int mode, double lambda) {
-  double part[2];
-  lba_reduce_lane(w, threadIdx.x, mode, lambda, part);
-  const double chi = lba_tree(part[0]);
-  double other;
-  if (mode) {
-    other = lba_tree(part[1]);
-  } else {
-    other = part[1];
-#pragma unroll
-    for (int stride = LBA_LANES / 2; stride >= 1; stride >>= 1) {
-      const double o = __shfl_down(other, stride);
-      other = o > other ? o : other;
-    }
-  }
-  if (threadIdx.x == 0) lba_reduce_finish(w, mode, lambda, chi, other);
-}
-
-__global__ __launch_bounds__(LBA_BLOCK) void k_lba_classify(LbaWs w, uint8_t* flag) {
-  const int e = blockIdx.x * LBA_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(BA_BLOCK) void k_lba_classify(LbaWs w, uint8_t* flag) {
+  const int e = blockIdx.x * BA_BLOCK + threadIdx.x;
   if (e < w.ne) flag[e] = lba_edge_flag(w, e) ? 1 : 0;
 }
 
@@ -185,58 +123,12 @@ struct orbfe_lba {
   uint8_t* d_flag = nullptr;
 };
 
-static size_t lba_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // carves the device pool; with base == nullptr only the size is computed
 static size_t lba_carve(orbfe_lba* h, uint8_t* base) {
-  size_t off = 0;
-  const size_t nk = h->max_kf, nf = h->max_free, np = h->max_points, ne = h->max_edges, n = 6 * nf;
-  LbaWs& w = h->w;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += lba_al(bytes);
-    return p;
-  };
-#define LBA_TAKE(field, type, count) w.field = reinterpret_cast<type*>(take(sizeof(type) * (count)))
-  LBA_TAKE(cam, const double, 5 * nk);
-  LBA_TAKE(kf_free, const int, nk);
-  LBA_TAKE(edge_begin, const int, np + 1);
-  LBA_TAKE(e_kf, const int, ne);
-  LBA_TAKE(e_pt, const int, ne);
-  LBA_TAKE(e_obs, const double, 3 * ne);
-  LBA_TAKE(e_w, const double, ne);
-  LBA_TAKE(e_stereo, const uint8_t, ne);
-  LBA_TAKE(kl_begin, const int, nf * LBA_LANES + 1);
-  LBA_TAKE(kl_edge, const int, ne);
-  LBA_TAKE(e_active, const uint8_t, ne);
-  LBA_TAKE(p_active, const uint8_t, np);
-  LBA_TAKE(slot_of_free, const int, nf);
-  LBA_TAKE(free_of_slot, const int, nf);
-  LBA_TAKE(est_T, double, 7 * nk);
-  LBA_TAKE(tri_T, double, 7 * nk);
-  LBA_TAKE(est_X, double, 3 * np);
-  LBA_TAKE(tri_X, double, 3 * np);
-  LBA_TAKE(e_err, double, 3 * ne);
-  LBA_TAKE(e_prod, double, LBA_EDGE_DOUBLES * ne);
-  LBA_TAKE(p_hll, double, 9 * np);
-  LBA_TAKE(p_bl, double, 3 * np);
-  LBA_TAKE(p_chi, double, np);
-  LBA_TAKE(p_dinv, double, 9 * np);
-  LBA_TAKE(p_db, double, 3 * np);
-  LBA_TAKE(p_xl, double, 3 * np);
-  LBA_TAKE(hpp, double, 21 * nf);
-  LBA_TAKE(bp, double, 6 * nf);
-  LBA_TAKE(S, double, n * n);
-  LBA_TAKE(bs, double, n);
-  LBA_TAKE(Lm, double, n * n);
-  LBA_TAKE(Mm, double, n * n);
-  LBA_TAKE(d, double, n);
-  LBA_TAKE(y, double, n);
-  LBA_TAKE(xp, double, n);
-  LBA_TAKE(rec, LmRec, 1);
-#undef LBA_TAKE
-  h->d_flag = take(ne);
-  return off;
+  BaPool pool = {base};
+  ba_carve(pool, h->w, h->max_kf, h->max_free, h->max_points, h->max_edges, true);
+  pool.take(h->d_flag, h->max_edges);
+  return pool.off;
 }
 
 extern "C" int orbfe_lba_create(int device, int max_free_kf, int max_kf, int max_points, int max_edges, orbfe_lba** out) {
@@ -295,109 +187,35 @@ extern "C" int orbfe_lba_destroy(orbfe_lba* h) {
 }
 
 namespace {
-inline unsigned lba_grid(int n) { return (unsigned)((n + LBA_BLOCK - 1) / LBA_BLOCK); }
+const BaNames kLbaNames = {"k_lba_edge",   "k_lba_point",      "k_lba_pose",      "k_lba_dinv",
+                           "k_lba_update", "k_lba_edge_trial", "k_lba_point_chi", "k_lba_reduce"};
 
-// lba_run's backend over the handle's device workspace
-struct LbaDevBackend {
+// lba_run's backend: BaDevBackend with the dense Schur complement, k_lba_ldlt and the classification
+struct LbaDevBackend : BaDevBackend {
   orbfe_lba* h;
-  LbaWs w;
-
-  template <class T>
-  int up(const T* dst, const T* src, size_t count) {
-    if (count == 0) return ORBFE_OK;
-    ORBFE_HIP_CHECK(hipMemcpyAsync(const_cast<T*>(dst), src, sizeof(T) * count, hipMemcpyHostToDevice, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));  // the source may be pageable and short-lived
-    return ORBFE_OK;
-  }
 
   int start(const LbaPlan& P) {
     w = h->w;
-    w.nk = P.nk, w.nfree = P.nfree, w.np = P.np, w.ne = P.ne, w.nslot = 0, w.kernel_on = 1;
     lba_set_deltas(&w);
-    int st;
-#define LBA_UP(dst, src, count) \
-  if ((st = up(dst, src, count)) != ORBFE_OK) return st
-    LBA_UP(w.cam, P.cam.data(), P.cam.size());
-    LBA_UP(w.kf_free, P.kf_free.data(), P.kf_free.size());
-    LBA_UP(w.edge_begin, P.edge_begin, (size_t)P.np + 1);
-    LBA_UP(w.e_kf, P.e_kf, (size_t)P.ne);
-    LBA_UP(w.e_pt, P.e_pt.data(), P.e_pt.size());
-    LBA_UP(w.e_obs, P.e_obs.data(), P.e_obs.size());
-    LBA_UP(w.e_w, P.e_w.data(), P.e_w.size());
-    LBA_UP(w.e_stereo, P.e_stereo.data(), P.e_stereo.size());
-    LBA_UP(w.kl_begin, P.kl_begin.data(), P.kl_begin.size());
-    LBA_UP(w.kl_edge, P.kl_edge.data(), P.kl_edge.size());
-    LBA_UP((const double*)w.est_T, P.T0.data(), P.T0.size());
-    LBA_UP((const double*)w.tri_T, P.T0.data(), P.T0.size());
-    LBA_UP((const double*)w.est_X, P.X0.data(), P.X0.size());
-    LBA_UP((const double*)w.tri_X, P.X0.data(), P.X0.size());
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.e_err, 0, sizeof(double) * 3 * (size_t)P.ne, h->stream));
-    return ORBFE_OK;
+    return BaDevBackend::start(P);
   }
 
-  int begin_round(const LbaActive& A, bool kernel_on) {
-    int st;
-    LBA_UP(w.e_active, A.e_active.data(), A.e_active.size());
-    LBA_UP(w.p_active, A.p_active.data(), A.p_active.size());
-    LBA_UP(w.slot_of_free, A.slot_of_free.data(), A.slot_of_free.size());
-    LBA_UP(w.free_of_slot, A.free_of_slot.data(), A.free_of_slot.size());
-#undef LBA_UP
-    w.nslot = A.nslot, w.kernel_on = kernel_on ? 1 : 0;
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.xp, 0, sizeof(double) * 6 * (size_t)w.nfree, h->stream));
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.p_xl, 0, sizeof(double) * 3 * (size_t)w.np, h->stream));
-    return ORBFE_OK;
-  }
-
-  int read_rec(LmRec* out) {
-    ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_rec, w.rec, sizeof(LmRec), hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
-    *out = *h->h_rec;
-    return ORBFE_OK;
-  }
-
-  int linearize(LmRec* out) {
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LmRec), h->stream));
-    ORBFE_LAUNCH("k_lba_edge", k_lba_edge<true>, dim3(lba_grid(w.ne)), dim3(LBA_BLOCK), 0, h->stream, w, 0);
-    ORBFE_LAUNCH("k_lba_point", k_lba_point<true>, dim3(lba_grid(w.np)), dim3(LBA_BLOCK), 0, h->stream, w);
-    if (w.nslot > 0) ORBFE_LAUNCH("k_lba_pose", k_lba_pose, dim3(w.nslot), dim3(LBA_LANES), 0, h->stream, w);
-    ORBFE_LAUNCH("k_lba_reduce", k_lba_reduce, dim3(1), dim3(LBA_LANES), 0, h->stream, w, 0, 0.0);
-    return read_rec(out);
-  }
+  int begin_round(const LbaActive& A, bool kernel_on) { return BaDevBackend::begin_round(A, kernel_on, 6 * (size_t)w.nfree); }
 
   int trial(double lambda, LmRec* out) {
-    ORBFE_HIP_CHECK(hipMemsetAsync(w.rec, 0, sizeof(LmRec), h->stream));
-    ORBFE_LAUNCH("k_lba_dinv", k_lba_dinv, dim3(lba_grid(w.np)), dim3(LBA_BLOCK), 0, h->stream, w, lambda);
+    int st = begin_trial(lambda);
+    if (st != ORBFE_OK) return st;
     if (w.nslot > 0)
-      ORBFE_LAUNCH("k_lba_schur", k_lba_schur, dim3(w.nslot, w.nslot), dim3(LBA_LANES), 0, h->stream, w, lambda);
-    ORBFE_LAUNCH("k_lba_ldlt", k_lba_ldlt, dim3(1), dim3(LBA_LDLT_THREADS), 0, h->stream, w);
-    ORBFE_LAUNCH("k_lba_update", k_lba_update, dim3(lba_grid(w.np + w.nk)), dim3(LBA_BLOCK), 0, h->stream, w);
-    ORBFE_LAUNCH("k_lba_edge_trial", k_lba_edge<false>, dim3(lba_grid(w.ne)), dim3(LBA_BLOCK), 0, h->stream, w, 1);
-    ORBFE_LAUNCH("k_lba_point_chi", k_lba_point<false>, dim3(lba_grid(w.np)), dim3(LBA_BLOCK), 0, h->stream, w);
-    ORBFE_LAUNCH("k_lba_reduce", k_lba_reduce, dim3(1), dim3(LBA_LANES), 0, h->stream, w, 1, lambda);
-    return read_rec(out);
-  }
-
-  int accept() {  // discardTop: the trial estimates become the accepted ones
-    double* t = w.est_T;
-    w.est_T = w.tri_T, w.tri_T = t;
-    t = w.est_X;
-    w.est_X = w.tri_X, w.tri_X = t;
-    return ORBFE_OK;
+      ORBFE_LAUNCH("k_lba_schur", k_lba_schur, dim3(w.nslot, w.nslot), dim3(LBA_LANES), 0, stream, w, lambda);
+    ORBFE_LAUNCH("k_lba_ldlt", k_lba_ldlt, dim3(1), dim3(LBA_LDLT_THREADS), 0, stream, w);
+    return end_trial(lambda, out);
   }
 
   int classify(uint8_t* flag) {
-    ORBFE_LAUNCH("k_lba_classify", k_lba_classify, dim3(lba_grid(w.ne)), dim3(LBA_BLOCK), 0, h->stream, w, h->d_flag);
+    ORBFE_LAUNCH("k_lba_classify", k_lba_classify, dim3(ba_grid(w.ne)), dim3(BA_BLOCK), 0, stream, w, h->d_flag);
     ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(flag, h->d_flag, (size_t)w.ne, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return ORBFE_OK;
-  }
-
-  int finish(double* T, double* X) {
-    ORBFE_HIP_CHECK(hipMemcpyAsync(T, w.est_T, sizeof(double) * 7 * (size_t)w.nk, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipMemcpyAsync(X, w.est_X, sizeof(double) * 3 * (size_t)w.np, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    ORBFE_HIP_CHECK(hipMemcpyAsync(flag, h->d_flag, (size_t)w.ne, hipMemcpyDeviceToHost, stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(stream));
     return ORBFE_OK;
   }
 };
@@ -418,20 +236,7 @@ static int lba_check(const orbfe_lba* h, const orbfe_lba_problem_t* p, const orb
   int nfree = 0;
   for (int i = 0; i < p->n_kf; i++) nfree += p->fixed[i] ? 0 : 1;
   if (nfree > h->max_free) return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_lba_solve: free keyframes above the handle's bound");
-  if (p->edge_begin[0] != 0 || p->edge_begin[p->n_points] != p->n_edges)
-    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_lba_solve: edge_begin is not a CSR over n_edges");
-  std::vector<int> seen(p->n_kf > 0 ? p->n_kf : 1, -1);
-  for (int q = 0; q < p->n_points; q++) {
-    const int b = p->edge_begin[q], e = p->edge_begin[q + 1];
-    if (b > e || b < 0 || e > p->n_edges) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_lba_solve: edge_begin is not a CSR over n_edges");
-    for (int i = b; i < e; i++) {
-      const int kf = p->edge_kf[i];
-      if (kf < 0 || kf >= p->n_kf) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_lba_solve: keyframe index out of range");
-      if (seen[kf] == q) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_lba_solve: a keyframe listed twice under one point");
-      seen[kf] = q;
-    }
-  }
-  return ORBFE_OK;
+  return ba_check_csr("orbfe_lba_solve", p->n_kf, p->n_points, p->n_edges, p->edge_begin, p->edge_kf);
 }
 
 extern "C" int orbfe_lba_solve(orbfe_lba* h, const orbfe_lba_problem_t* p, orbfe_lba_result_t* r) {
@@ -445,7 +250,7 @@ extern "C" int orbfe_lba_solve(orbfe_lba* h, const orbfe_lba_problem_t* p, orbfe
   lba_plan(in, &plan);
   LbaOut o;
   ORBFE_HIP_CHECK(hipSetDevice(h->device));
-  LbaDevBackend b = {h, h->w};
+  LbaDevBackend b = {{h->stream, h->h_rec, h->w, &kLbaNames}, h};
   st = lba_run(b, in, plan, &o);
   if (st != ORBFE_OK) return st;
   if (p->n_kf > 0) memcpy(r->tcw, o.tcw.data(), sizeof(float) * o.tcw.size());

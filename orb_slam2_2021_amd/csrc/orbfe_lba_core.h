@@ -624,6 +624,17 @@ inline int lba_round(B& b, const LbaActive& A, bool kernel_on, int max_it, LbaPo
   return 0;
 }
 
+// A keyframe's state q (x y z w), t as the 12 floats of Tcw: to_homogeneous_matrix, narrowed by
+// Converter::toCvMat. Which keyframes are written out is each caller's rule.
+inline void lba_pose_out(const double* T, float* tcw) {
+  double m[9];
+  po_quat_to_matrix(T, m);
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) tcw[4 * r + c] = (float)m[3 * r + c];
+    tcw[4 * r + 3] = (float)T[4 + r];
+  }
+}
+
 // Optimizer.cc:658-781. B also supplies start, classify and finish.
 template <class B>
 inline int lba_run(B& b, const LbaIn& in, const LbaPlan& P, LbaOut* o) {
@@ -656,51 +667,41 @@ inline int lba_run(B& b, const LbaIn& in, const LbaPlan& P, LbaOut* o) {
     o->rounds[o->rounds_run - 1].n_flagged = o->n_erase;
     std::vector<double> T(7 * (size_t)in.nk), X(3 * (size_t)in.np);
     if ((st = b.finish(T.data(), X.data()))) return st;
-    for (int i = 0; i < in.nk; i++) {
-      if (in.fixed[i]) continue;  // a fixed keyframe's pose is not set (a local one with mnId 0: its input bits)
-      double m[9];
-      po_quat_to_matrix(&T[7 * (size_t)i], m);  // to_homogeneous_matrix, narrowed by Converter::toCvMat
-      for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) o->tcw[12 * (size_t)i + 4 * r + c] = (float)m[3 * r + c];
-        o->tcw[12 * (size_t)i + 4 * r + 3] = (float)T[7 * (size_t)i + 4 + r];
-      }
-    }
+    for (int i = 0; i < in.nk; i++)  // a fixed keyframe's pose is not set (a local one with mnId 0: its input bits)
+      if (!in.fixed[i]) lba_pose_out(&T[7 * (size_t)i], &o->tcw[12 * (size_t)i]);
     for (size_t i = 0; i < X.size(); i++) o->xw[i] = (float)X[i];
   }
   o->polls = poll.polls;
   return 0;
 }
 
-// The workspace in host memory, every stage a loop over the per-element functions
-struct LbaHostBackend {
+// The workspace in host memory, every stage a loop over the per-element functions: what the local and the
+// global adjuster's host backends (LbaHostBackend below, GbaHostBackend of orbfe_gba_core.h) share. Each
+// adds its reduced system's arrays and its trial: Dinv, its own Schur complement and solve into y, trial_tail.
+struct BaHostBackend {
   LbaWs w;
   LmRec rec;
-  const LbaPlan* P = nullptr;
   LbaActive A;
-  std::vector<double> est_T, tri_T, est_X, tri_X, e_err, e_prod, p_hll, p_bl, p_chi, p_dinv, p_db, p_xl, hpp, bp, S, bs, Lm, Mm,
-      d, y, xp, xnew;
+  std::vector<double> est_T, tri_T, est_X, tri_X, e_err, e_prod, p_hll, p_bl, p_chi, p_dinv, p_db, p_xl, hpp, bp, bs, d, y, xp;
 
-  int start(const LbaPlan& plan) {
-    P = &plan;
+  // n: the bound on the reduced system's size; the caller sets its own arrays and deltas after it
+  void start(const LbaPlan& plan, size_t n) {
     memset(&w, 0, sizeof(w));
-    const size_t nk = plan.nk, np = plan.np, ne = plan.ne, nf = plan.nfree, n = 6 * nf;
+    const size_t nk = plan.nk, np = plan.np, ne = plan.ne, nf = plan.nfree;
     est_T = plan.T0, tri_T = plan.T0, est_X = plan.X0, tri_X = plan.X0;
     e_err.assign(3 * ne, 0.0), e_prod.assign(LBA_EDGE_DOUBLES * ne, 0.0);
     p_hll.assign(9 * np, 0.0), p_bl.assign(3 * np, 0.0), p_chi.assign(np, 0.0), p_dinv.assign(9 * np, 0.0);
     p_db.assign(3 * np, 0.0), p_xl.assign(3 * np, 0.0);
-    hpp.assign(21 * nf, 0.0), bp.assign(6 * nf, 0.0), S.assign(n * n, 0.0), bs.assign(n, 0.0), Lm.assign(n * n, 0.0);
-    Mm.assign(n * n, 0.0), d.assign(n, 0.0), y.assign(n, 0.0), xp.assign(n, 0.0), xnew.assign(n, 0.0);
+    hpp.assign(21 * nf, 0.0), bp.assign(6 * nf, 0.0), bs.assign(n, 0.0), d.assign(n, 0.0), y.assign(n, 0.0), xp.assign(n, 0.0);
     w.nk = (int)nk, w.nfree = (int)nf, w.np = (int)np, w.ne = (int)ne;
     w.cam = plan.cam.data(), w.kf_free = plan.kf_free.data(), w.e_pt = plan.e_pt.data(), w.e_obs = plan.e_obs.data();
     w.e_w = plan.e_w.data(), w.e_stereo = plan.e_stereo.data(), w.kl_begin = plan.kl_begin.data(), w.kl_edge = plan.kl_edge.data();
     w.est_T = est_T.data(), w.tri_T = tri_T.data(), w.est_X = est_X.data(), w.tri_X = tri_X.data();
     w.e_err = e_err.data(), w.e_prod = e_prod.data(), w.p_hll = p_hll.data(), w.p_bl = p_bl.data(), w.p_chi = p_chi.data();
-    w.p_dinv = p_dinv.data(), w.p_db = p_db.data(), w.p_xl = p_xl.data(), w.hpp = hpp.data(), w.bp = bp.data(), w.S = S.data();
-    w.bs = bs.data(), w.Lm = Lm.data(), w.Mm = Mm.data(), w.d = d.data(), w.y = y.data(), w.xp = xp.data();
+    w.p_dinv = p_dinv.data(), w.p_db = p_db.data(), w.p_xl = p_xl.data(), w.hpp = hpp.data(), w.bp = bp.data();
+    w.bs = bs.data(), w.d = d.data(), w.y = y.data(), w.xp = xp.data();
     w.edge_begin = plan.edge_begin, w.e_kf = plan.e_kf;
     w.rec = &rec;
-    lba_set_deltas(&w);
-    return 0;
   }
 
   int begin_round(const LbaActive& a, bool kernel_on) {
@@ -744,6 +745,48 @@ struct LbaHostBackend {
     return 0;
   }
 
+  // after the pose solve, y the solution unless the trial has failed: x and the points' back-substitution,
+  // the update, the trial chi2
+  int trial_tail(double lambda, LmRec* out) {
+    if (!rec.fail) {
+      for (int i = 0; i < 6 * w.nslot; i++) w.xp[i] = w.y[i];
+      for (int p = 0; p < w.np; p++) lba_point_backsub(w, p);
+    }
+    for (int p = 0; p < w.np; p++) lba_update_point(w, p);
+    for (int k = 0; k < w.nk; k++) lba_update_kf(w, k);
+    const int fail = rec.fail;
+    const uint32_t fl = rec.flags;
+    tree_reduce(1, lambda, true);
+    rec.fail = fail, rec.flags = fl;
+    *out = rec;
+    return 0;
+  }
+
+  int accept() {
+    est_T.swap(tri_T), est_X.swap(tri_X);
+    w.est_T = est_T.data(), w.tri_T = tri_T.data(), w.est_X = est_X.data(), w.tri_X = tri_X.data();
+    return 0;
+  }
+
+  int finish(double* T, double* X) {
+    memcpy(T, est_T.data(), 8 * est_T.size());
+    memcpy(X, est_X.data(), 8 * est_X.size());
+    return 0;
+  }
+};
+
+struct LbaHostBackend : BaHostBackend {
+  std::vector<double> S, Lm, Mm;
+
+  int start(const LbaPlan& plan) {
+    const size_t n = 6 * (size_t)plan.nfree;
+    BaHostBackend::start(plan, n);
+    S.assign(n * n, 0.0), Lm.assign(n * n, 0.0), Mm.assign(n * n, 0.0);
+    w.S = S.data(), w.Lm = Lm.data(), w.Mm = Mm.data();
+    lba_set_deltas(&w);
+    return 0;
+  }
+
   int trial(double lambda, LmRec* out) {
     memset(&rec, 0, sizeof(rec));
     const int n = 6 * w.nslot;
@@ -776,33 +819,12 @@ struct LbaHostBackend {
       for (int i = 0; i < n; i++) w.y[i] = w.y[i] / w.d[i];
       for (int k = n - 1; k >= 0; k--)
         for (int i = 0; i < k; i++) w.y[i] = w.y[i] - w.Lm[(size_t)i * n + k] * w.y[k];
-      for (int i = 0; i < n; i++) w.xp[i] = w.y[i];
-      for (int p = 0; p < w.np; p++) lba_point_backsub(w, p);
     }
-    for (int p = 0; p < w.np; p++) lba_update_point(w, p);
-    for (int k = 0; k < w.nk; k++) lba_update_kf(w, k);
-    const int fail = rec.fail;
-    const uint32_t fl = rec.flags;
-    tree_reduce(1, lambda, true);
-    rec.fail = fail, rec.flags = fl;
-    *out = rec;
-    return 0;
-  }
-
-  int accept() {
-    est_T.swap(tri_T), est_X.swap(tri_X);
-    w.est_T = est_T.data(), w.tri_T = tri_T.data(), w.est_X = est_X.data(), w.tri_X = tri_X.data();
-    return 0;
+    return trial_tail(lambda, out);
   }
 
   int classify(uint8_t* flag) {
     for (int e = 0; e < w.ne; e++) flag[e] = lba_edge_flag(w, e) ? 1 : 0;
-    return 0;
-  }
-
-  int finish(double* T, double* X) {
-    memcpy(T, est_T.data(), 8 * est_T.size());
-    memcpy(X, est_X.data(), 8 * est_X.size());
     return 0;
   }
 };

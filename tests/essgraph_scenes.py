@@ -114,6 +114,16 @@ def graph(n, band=1, fixed=0, n_corr=2, loop_rows=1, fix_scale=True, seed=0, dri
 # search over seeds 0 .. 39 of this generator with tests/essgraph_ref.py (the first hit of three).
 REJECTED_SEED = 14
 
+def _nonfinite():
+    """The corrected keyframe's translation is 1e160: finite, but the squares of the residuals of its two
+    edges are not, so chi2 is +inf and H has non-finite entries from the third block row on. Every trial's
+    factorisation passes two pivot blocks, fails at the third and is rejected."""
+    p = graph(5, n_corr=1, seed=12, corr_rot=0.03)
+    p.corrected_sim3 = p.corrected_sim3.copy()
+    p.corrected_sim3[0, 4:7] = [1e160, -1e160, 1e160]
+    return p
+
+
 CASES = {
     # 2 vertices, 1 edge, one fixed: a 1-block system; one point
     "pair": lambda: graph(2, n_corr=1, seed=1, corr_rot=0.05, n_points=1),
@@ -135,6 +145,7 @@ CASES = {
     "log_branches": lambda: graph(7, n_corr=3, seed=10, fix_scale=False, loop_rows=0, drift=(0.0, 0.0),
                                   per_vertex_corr=[([0.0, 0.0, 0.0], 1.3), ([0.0, 0.3, 0.0], 1.0), ([0.2, 0.0, 0.1], 1.0)]),
     "rejected": lambda: graph(6, n_corr=2, seed=REJECTED_SEED, corr_rot=3.0, corr_scale=0.3, fix_scale=False),
+    "nonfinite": _nonfinite,
 }
 
 GPU_CASES = list(CASES)

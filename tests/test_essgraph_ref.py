@@ -147,7 +147,7 @@ def densify(S, lam):
     return A
 
 
-FINITE_CASES = list(CASES)
+FINITE_CASES = [n for n in CASES if n != "nonfinite"]  # that scene's system has no solution to compare
 
 
 def test_envelope_step_against_numpy_and_dense_ldlt():
@@ -217,7 +217,15 @@ def test_each_scene_takes_its_branch():
     assert seen == {(True, True), (True, False), (False, True), (False, False)}
     t = ref("rejected").trace
     assert 0 < t.rejected_trials < t.trials and t.rejected_trials % 10 != 0 and t.stop != P.STOP_TERMINATE
-    assert all(ref(n).trace.flags == 0 for n in CASES)
+    assert all(ref(n).trace.flags == 0 for n in FINITE_CASES)
+    r = ref("nonfinite")
+    t = r.trace
+    assert t.flags & R.FLAG_NONFINITE and t.rejected_trials >= 1 and t.rejected_trials == t.trials
+    assert t.chi2 == math.inf and all(cur == ini for ini, cur in t.chis)  # no trial was accepted
+    S = R.Solver(case("nonfinite"))
+    S.linearize()
+    bad = [i // 7 for i in range(7 * S.ns) if not all(math.isfinite(v) for v in S.rows[i])]
+    assert S.ns == 4 and min(bad) == 2  # two pivot blocks factor before the failing one
 
 
 def test_point_correction_against_numpy():
