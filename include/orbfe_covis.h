@@ -15,6 +15,8 @@
  * index, 0 <= id < max_point_id) in each keypoint slot, -1 for none; one bad flag per point id.
  * The inverse (point -> observing keyframes and slot, the reference's mObservations) is not an
  * input: it is derived on the device from the rows and rebuilt by the next query after a mutation.
+ * The cullings at the end of this header (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag's
+ * EraseObservation cascade, LocalMapping::MapPointCulling) walk the same state and prune it in place.
  * Rules of that derivation:
  *   - A point's observers are the distinct keyframes whose row holds it, ascending in keyframe
  *     mnId. The slot recorded for a keyframe is the lowest one holding the point (the reference's
@@ -28,6 +30,13 @@
  *     as an entry of a vote list, as a point of a local row.
  *   - The rebuilt inverse is identical from run to run: every point's segment is put in
  *     (keyframe mnId, slot) order after the atomics have filled it.
+ *   - Observations() (MapPoint::nObs) is derived too: the sum, over a point's distinct live
+ *     observers, of 1 + STEREO(the observer's attribute byte at its recorded (lowest) slot). The
+ *     octave KeyFrameCulling reads for an observer is the one at that same recorded slot.
+ *
+ * Attributes. One byte per row slot beside the rows (orbfe_covis_set_keyframe_attrs): what the two
+ * cullings read of a keypoint. They are never part of the inverse; the three queries below do not
+ * read them.
  *
  * The tie key. The reference orders keyframes by KeyFrame* (std::map<KeyFrame*, int> iteration,
  * sort of pair<int, KeyFrame*>), so equal weights are ordered by pointer value. tie_key stands for
@@ -54,8 +63,8 @@ typedef struct orbfe_covis orbfe_covis;
 #define ORBFE_COVIS_MAX_SLOTS 8192
 #define ORBFE_COVIS_MAX_POINT_ID (1 << 24)
 
-/* device < 0: a host-only handle (bookkeeping and argument checks work, the three queries return
- * ORBFE_ERR_STATE after their argument checks). */
+/* device < 0: a host-only handle (bookkeeping and argument checks work, the queries and the two
+ * cullings return ORBFE_ERR_STATE after their argument checks). */
 int orbfe_covis_create(int device, int max_keyframes, int max_slots, int max_point_id,
                        orbfe_covis** out);
 int orbfe_covis_destroy(orbfe_covis* h);
@@ -152,6 +161,57 @@ typedef struct {
 
 int orbfe_covis_local_map(orbfe_covis* h, int n_local, const int64_t* local_kf_ids,
                           orbfe_covis_local_map_t* result);
+
+/* The per-slot attributes of a stored keyframe: bits 0-4 mvKeysUn[i].octave, bit 5 mvuRight[i] >= 0,
+ * bit 6 mvDepth[i] > mThDepth || mvDepth[i] < 0 as the caller evaluates it in float. n_slots other than
+ * the stored row's length, or bit 7 set: ORBFE_ERR_ARG; an id that is not stored: ORBFE_ERR_STATE.
+ * A keyframe's keypoints never change: set_keyframe on a stored keyframe keeps the attributes when the
+ * row's length is unchanged and drops them when it differs; erase_keyframe and clear drop them. */
+#define ORBFE_COVIS_ATTR_OCTAVE 0x1f
+#define ORBFE_COVIS_ATTR_STEREO 0x20
+#define ORBFE_COVIS_ATTR_FAR 0x40
+int orbfe_covis_set_keyframe_attrs(orbfe_covis* h, int64_t kf_id, int n_slots, const uint8_t* attrs);
+
+/* LocalMapping::KeyFrameCulling (LocalMapping.cc:640-706) over kf_ids, the current keyframe's
+ * GetVectorCovisibleKeyFrames() in the caller's order, with what KeyFrame::SetBadFlag does to the map's
+ * observations (KeyFrame.cc:486-488, MapPoint.cc:141-198). Candidates are decided in order and each sees
+ * the culls before it:
+ *   - a slot counts towards nMPs when it holds a point that is not bad and, unless monocular, its FAR
+ *     bit is clear; it is redundant when Observations() > 3 (the candidate included) and at least 3
+ *     other observers have octave <= the slot's octave + 1;
+ *   - n_redundant > 0.9 * n_mps (an int against a double product) culls; n_mps == 0 keeps;
+ *   - mnId 0 is skipped (3); a redundant candidate with not_erase[i] != 0 is reported (2, the
+ *     reference's mbToBeErased) and changes nothing;
+ *   - a culled keyframe leaves the table as by erase_keyframe; each point its row holds (at the first
+ *     slot holding it, bad points skipped) loses the observer, and one whose Observations() falls to
+ *     <= 2 gets the bad flag, is listed, and its id at the recorded slot of every remaining observer's
+ *     row becomes -1 (EraseMapPointMatch(mit->second): that slot alone).
+ * The inverse is left stale. Dependent device steps: keyframes culled + 1, each one 4-byte read-back.
+ * Checks, before any device work: each id stored and named once, else ORBFE_ERR_ARG; every stored
+ * keyframe has attributes, else ORBFE_ERR_STATE; bad_capacity, else ORBFE_ERR_CAPACITY. */
+typedef struct {
+  uint8_t* decision;     /* [n] 0 kept, 1 culled, 2 redundant but not_erase (mbToBeErased), 3 skipped (mnId 0) */
+  int32_t* n_mps;        /* [n] nMPs as the reference counts it at this candidate's turn */
+  int32_t* n_redundant;  /* [n] nRedundantObservations at this candidate's turn */
+  int32_t* bad_begin;    /* [n + 1] CSR over the candidates into bad_points */
+  int32_t* bad_points;   /* [bad_capacity] the points a culled candidate's EraseObservation made bad, in slot order */
+  int bad_capacity;      /* in: >= the sum of the candidates' row lengths, else ORBFE_ERR_CAPACITY before anything runs */
+} orbfe_covis_cull_t;
+
+int orbfe_covis_cull_keyframes(orbfe_covis* h, int n, const int64_t* kf_ids, const uint8_t* not_erase,
+                               int monocular, orbfe_covis_cull_t* result);
+
+/* LocalMapping::MapPointCulling (LocalMapping.cc:174-209) over mlpRecentAddedMapPoints, one point each:
+ *   1 leaves (was bad); 2 set bad: (float)found / visible < 0.25f (0/0 is NaN and is not <);
+ *   3 set bad: (int)current - (int)first >= 2 and Observations() <= (monocular ? 2 : 3);
+ *   4 leaves: the age >= 3; 0 stays in the list.
+ * Actions 2 and 3 flag the point and write -1 at its observers' recorded slots, as above; the inverse is
+ * left stale then. One launch, one result copy. A point named twice, an id outside [0, max_point_id),
+ * a keyframe id outside [0, 2^31): ORBFE_ERR_ARG, nothing touched; a stored keyframe without
+ * attributes: ORBFE_ERR_STATE. */
+int orbfe_covis_cull_points(orbfe_covis* h, int n, const int32_t* point_ids, const int32_t* found,
+                            const int32_t* visible, const int64_t* first_kf_id, int64_t current_kf_id,
+                            int monocular, uint8_t* action);
 
 #ifdef __cplusplus
 }

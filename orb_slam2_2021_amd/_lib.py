@@ -136,6 +136,11 @@ class covis_local_map(Structure):
                 ("fixed_ids", c_void_p), ("edge_begin", c_void_p), ("edge_kf", c_void_p), ("edge_slot", c_void_p)]
 
 
+class covis_cull(Structure):
+    _fields_ = [("decision", c_void_p), ("n_mps", c_void_p), ("n_redundant", c_void_p), ("bad_begin", c_void_p),
+                ("bad_points", c_void_p), ("bad_capacity", c_int)]
+
+
 class sim3_solver(Structure):  # orbfe_sim3.h
     _fields_ = [("n", c_int), ("x3dc1", c_void_p), ("x3dc2", c_void_p), ("sigma2_1", c_void_p),
                 ("sigma2_2", c_void_p), ("k1", c_float * 4), ("k2", c_float * 4), ("fix_scale", c_int),
@@ -566,6 +571,10 @@ _SIGNATURES = {
     "orbfe_covis_update_connections": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(covis_connections)]),
     "orbfe_covis_vote": (c_int, [c_void_p, c_int, c_void_p, c_void_p, POINTER(covis_votes)]),
     "orbfe_covis_local_map": (c_int, [c_void_p, c_int, c_void_p, POINTER(covis_local_map)]),
+    "orbfe_covis_set_keyframe_attrs": (c_int, [c_void_p, ctypes.c_int64, c_int, c_void_p]),
+    "orbfe_covis_cull_keyframes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(covis_cull)]),
+    "orbfe_covis_cull_points": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64,
+                                        c_int, c_void_p]),
     # orbfe_poseopt.h
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),

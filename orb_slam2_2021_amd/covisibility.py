@@ -6,7 +6,9 @@ LocalBundleAdjustment's gather run over them there.
 (mConnectedKeyFrameWeights, mvpOrderedConnectedKeyFrames, mvOrderedWeights, mpParent, mspChildrens,
 mbFirstConnection). The device returns the counts and orders of src/KeyFrame.cc:304-378; the side
 effects (:360-392, AddConnection / UpdateBestCovisibles at :122-157) are applied here on the host,
-keyframe by keyframe. Keyframes are named by mnId; every order among equal weights is the tie
+keyframe by keyframe. LocalMapping::KeyFrameCulling and MapPointCulling run over the same table
+(keyframe_culling, map_point_culling); what KeyFrame::SetBadFlag does to the graph and the spanning
+tree is applied here (set_bad_flag). Keyframes are named by mnId; every order among equal weights is the tie
 key's (the reference's KeyFrame* value; mnId unless given).
 """
 from __future__ import annotations
@@ -43,6 +45,7 @@ class CovisibilityGraph:
         L.check(self._lib.orbfe_covis_create(int(device), int(max_keyframes), int(max_slots), int(max_point_id),
                                              byref(h)), "orbfe_covis_create")
         self._h = h
+        self._max_slots = int(max_slots)
         self._kfdb = kfdb
         self._nodes: Dict[int, _Node] = {}
 
@@ -116,6 +119,145 @@ class CovisibilityGraph:
     def clear(self) -> None:
         L.check(self._lib.orbfe_covis_clear(self._h), "orbfe_covis_clear")
         self._nodes.clear()
+
+    # ---- culling ------------------------------------------------------------------------------
+    @staticmethod
+    def pack_attrs(octaves, u_right, depth, th_depth) -> np.ndarray:
+        """The attribute byte per keypoint: octave | STEREO (mvuRight[i] >= 0) | FAR (mvDepth[i] > mThDepth ||
+        mvDepth[i] < 0), the compares in float32 as the reference makes them."""
+        o = np.asarray(octaves, np.int64).reshape(-1)
+        if len(o) and (o.min() < 0 or o.max() > 31):
+            raise ValueError("octave outside 0..31")
+        ur = np.asarray(u_right, np.float32).reshape(-1)
+        d = np.asarray(depth, np.float32).reshape(-1)
+        if not len(o) == len(ur) == len(d):
+            raise ValueError("octaves / u_right / depth differ in length")
+        th = np.float32(th_depth)
+        far = (d > th) | (d < np.float32(0))
+        return np.ascontiguousarray(o.astype(np.uint8) | (np.uint8(0x20) * (ur >= np.float32(0)))
+                                    | (np.uint8(0x40) * far), np.uint8)
+
+    def set_keyframe_attrs(self, kf_id: int, octaves, u_right, depth, th_depth) -> None:
+        """What the cullings read of a stored keyframe's keypoints (mvKeysUn[i].octave, mvuRight, mvDepth against
+        mThDepth), one byte per slot. A keyframe's keypoints never change: once per keyframe is enough."""
+        a = self.pack_attrs(octaves, u_right, depth, th_depth)
+        L.check(self._lib.orbfe_covis_set_keyframe_attrs(self._h, int(kf_id), len(a), L.ptr(a)),
+                "orbfe_covis_set_keyframe_attrs")
+
+    def map_point_culling(self, point_ids, found, visible, first_kf_ids, current_kf_id: int,
+                          monocular: bool) -> np.ndarray:
+        """LocalMapping::MapPointCulling (LocalMapping.cc:174-209) over mlpRecentAddedMapPoints: per point 0 stays in
+        the list, 1 leaves (was bad), 2 set bad (found ratio), 3 set bad (observations), 4 leaves (age). Points set
+        bad are flagged in the table and erased from their observers' rows."""
+        p = np.ascontiguousarray(point_ids, np.int32)
+        f = np.ascontiguousarray(found, np.int32)
+        v = np.ascontiguousarray(visible, np.int32)
+        k = np.ascontiguousarray(first_kf_ids, np.int64)
+        if not len(p) == len(f) == len(v) == len(k):
+            raise ValueError("point_ids / found / visible / first_kf_ids differ in length")
+        action = np.zeros(max(len(p), 1), np.uint8)
+        L.check(self._lib.orbfe_covis_cull_points(self._h, len(p), L.ptr(p), L.ptr(f), L.ptr(v), L.ptr(k),
+                                                  int(current_kf_id), 1 if monocular else 0, L.ptr(action)),
+                "orbfe_covis_cull_points")
+        return action[:len(p)]
+
+    def cull_keyframes(self, kf_ids: Sequence[int], monocular: bool, not_erase=None) -> SimpleNamespace:
+        """orbfe_covis_cull_keyframes over the candidates in the given order, the table pruned and no graph state
+        touched: decision, n_mps, n_redundant per candidate and bad_points, one list per candidate."""
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        n = len(ids)
+        ne = np.zeros(max(n, 1), np.uint8) if not_erase is None else np.ascontiguousarray(not_erase, np.uint8)
+        if not_erase is not None and len(ne) != n:
+            raise ValueError("kf_ids / not_erase differ in length")
+        m = max(n, 1)
+        cap = max(n * self._max_slots, 1)
+        dec, mps, red = np.zeros(m, np.uint8), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        beg, pts = np.zeros(m + 1, np.int32), np.zeros(cap, np.int32)
+        r = L.covis_cull(decision=L.ptr(dec), n_mps=L.ptr(mps), n_redundant=L.ptr(red), bad_begin=L.ptr(beg),
+                         bad_points=L.ptr(pts), bad_capacity=cap)
+        L.check(self._lib.orbfe_covis_cull_keyframes(self._h, n, L.ptr(ids), L.ptr(ne), 1 if monocular else 0,
+                                                     byref(r)), "orbfe_covis_cull_keyframes")
+        return SimpleNamespace(decision=dec[:n].tolist(), n_mps=mps[:n].tolist(), n_redundant=red[:n].tolist(),
+                               bad_points=[pts[beg[i]:beg[i + 1]].tolist() for i in range(n)])
+
+    def keyframe_culling(self, kf_id: int, monocular: bool, not_erase=()) -> SimpleNamespace:
+        """LocalMapping::KeyFrameCulling (LocalMapping.cc:640-706) for mpCurrentKeyFrame = kf_id: the candidates are
+        GetVectorCovisibleKeyFrames(kf_id), `not_erase` the ids among them with mbNotErase. One device call decides
+        them in order and prunes the table; then, for each culled keyframe in order, the rest of
+        KeyFrame::SetBadFlag runs on the host graph (set_bad_flag's graph part). Returns the device's result with
+        kf_ids, culled (ids, in order) and to_be_erased (redundant but not_erase: the reference's mbToBeErased).
+        Poses are not graph state: mTcp = Tcw * parent's Twc (KeyFrame.cc:556) stays with the caller, who reads
+        GetParent before this call."""
+        cand = self.GetVectorCovisibleKeyFrames(kf_id)
+        hold = {int(i) for i in not_erase}
+        res = self.cull_keyframes(cand, monocular, [1 if i in hold else 0 for i in cand])
+        res.kf_ids = cand
+        res.culled = [i for i, d in zip(cand, res.decision) if d == 1]
+        res.to_be_erased = [i for i, d in zip(cand, res.decision) if d == 2]
+        before: Dict[int, List[int]] = {}
+        for i in res.culled:
+            self._set_bad_flag_graph(i, before)
+        self._mirror(before)
+        return res
+
+    def set_bad_flag(self, kf_id: int) -> None:
+        """KeyFrame::SetBadFlag (KeyFrame.cc:469-562) on the graph: EraseConnection on the connected keyframes, the
+        spanning-tree re-parenting of :496-553 in the reference's iteration orders, EraseChild, the database's
+        erase and the mirror. The keyframe's row leaves the table as by orbfe_covis_erase_keyframe; the
+        EraseObservation cascade on the points (:486-488) belongs to keyframe_culling, which runs it on the device.
+        mnId 0 is left alone (:473). mbNotErase and mTcp stay with the caller."""
+        kf_id = int(kf_id)
+        if kf_id == 0:
+            return
+        if kf_id not in self._nodes:
+            raise KeyError(kf_id)
+        L.check(self._lib.orbfe_covis_erase_keyframe(self._h, kf_id), "orbfe_covis_erase_keyframe")
+        before: Dict[int, List[int]] = {}
+        self._set_bad_flag_graph(kf_id, before)
+        self._mirror(before)
+
+    def _set_bad_flag_graph(self, kf_id: int, before: Dict[int, List[int]]) -> None:
+        node = self._nodes.pop(kf_id)
+        for other in sorted(node.weights, key=self._tie):  # :482-484, the map's iteration order
+            o = self._nodes.get(other)
+            if o is not None and kf_id in o.weights:
+                before.setdefault(other, list(o.ordered))
+                del o.weights[kf_id]
+                self._update_best_covisibles(o)
+        # :496-553. A set<KeyFrame*> iterates in tie-key order.
+        candidates = set() if node.parent is None else {node.parent}
+        children = {c for c in node.children if c in self._nodes}  # isBad() children are passed over for good
+        while children:
+            best, child, parent = -1, None, None
+            for c in sorted(children, key=self._tie):
+                cn = self._nodes[c]
+                for v in cn.ordered:
+                    for pc in sorted(candidates, key=self._tie):
+                        if v == pc:
+                            w = cn.weights.get(v, 0)
+                            if w > best:
+                                best, child, parent = w, c, v
+            if child is None:
+                break
+            self._change_parent(child, parent)
+            candidates.add(child)
+            children.discard(child)
+        for c in sorted(children, key=self._tie):  # :549-553
+            self._change_parent(c, node.parent)
+        if node.parent is not None and node.parent in self._nodes:
+            self._nodes[node.parent].children.discard(kf_id)  # :555
+        if self._kfdb is not None:  # :561
+            try:
+                self._kfdb.erase(kf_id)
+            except L.OrbfeError as e:
+                if e.status != L.ORBFE_ERR_STATE:  # the database never held it
+                    raise
+
+    def _change_parent(self, child: int, parent: Optional[int]) -> None:
+        """KeyFrame.cc:412-417"""
+        self._nodes[child].parent = parent
+        if parent is not None and parent in self._nodes:
+            self._nodes[parent].children.add(child)
 
     # ---- device queries -----------------------------------------------------------------------
     def count_connections(self, kf_ids: Sequence[int], th: int = 15) -> List[SimpleNamespace]:

@@ -36,6 +36,7 @@
 #include "../../include/orbfe.h"
 #include "../../include/orbfe_covis.h"
 #include "orbfe_covis_core.h"
+#include "orbfe_cull_core.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
 
@@ -396,6 +397,206 @@ __global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_lm_edges(const int3
   if ((unsigned)r < (unsigned)n_live) edge_kf[e] = order[r];
 }
 
+// ---- culling (orbfe_cull_core.h holds the per-item rules) -----------------------------------
+// The inverse is the one the call started with; what the call itself changes is read beside it: the
+// rows (a bad point's recorded slots become -1), the bad flags, and `culled`, indexed by mnId rank.
+// k_covis_cull_eval: one 256-thread workgroup per undecided candidate, threads stride over the slots.
+// k_covis_cull_commit: one 1024-thread workgroup applies the round's lowest culling candidate.
+// k_covis_cull_points: one thread per recent point.
+#define COVIS_CULL_NONE 0x7f7f7f7f  // a round's minimum before any candidate culls (memset bytes 0x7f)
+
+struct CovisCullArgs {
+  CovisTable t;
+  int M;
+  const uint8_t* attr;            // [M * S]
+  const int32_t* row_at_idrank;   // [n_live]
+  const int32_t* id_rank_of_row;  // [M]
+  int32_t* culled;                // [n_live] by mnId rank
+  const int32_t* cand_row;        // [n]
+  const uint8_t* cand_flag;       // [n] bit 0: not_erase, bit 1: mnId 0
+  int n, start, monocular;
+  uint8_t* decision;              // [n]
+  int32_t* n_mps;                 // [n]
+  int32_t* n_red;                 // [n]
+  int32_t* round_min;             // this round's lowest index that culls
+  int32_t* bad_count;             // [n]
+  int32_t* bad_list;              // [bad_cap]
+  int32_t* bad_cursor;            // entries of bad_list in use
+  int bad_cap;
+};
+
+// Observations() of p and the gated observers other than `self`, over the live observers that this
+// call has not culled. attr_slot: the candidate's byte at the querying slot.
+__device__ __forceinline__ void covis_cull_walk(const CovisCullArgs& a, int p, int self, uint8_t attr_slot,
+                                                int* obs_out, int* gated_out, int* self_slot_out) {
+  int obs = 0, gated = 0, self_slot = -1;
+  const int e1 = a.t.begin[p + 1];
+  for (int e = a.t.begin[p]; e < e1; e++) {
+    const uint32_t v = a.t.obs[e];
+    if (v >> 31) continue;  // the keyframe is recorded at its lowest slot
+    const int r = (int)((v >> 13) & 4095u);
+    if (r >= a.t.n_live) continue;
+    const int os = (int)(v & 8191u);
+    if (r == self) self_slot = os;
+    if (a.culled && a.culled[r]) continue;
+    const int orow = a.row_at_idrank[r];
+    if ((unsigned)orow >= (unsigned)a.M || os >= a.t.S) continue;
+    const uint8_t ao = a.attr[(size_t)orow * a.t.S + os];
+    obs += cull_weight(ao);
+    if (r != self && cull_gate(ao, attr_slot)) gated++;
+  }
+  *obs_out = obs;
+  *gated_out = gated;
+  *self_slot_out = self_slot;
+}
+
+// SetBadFlag of p: the flag, and -1 at the recorded slot of every observer still alive
+__device__ __forceinline__ void covis_cull_set_bad(const CovisCullArgs& a, int p, int self) {
+  a.t.bad[p] = 1;
+  if (p >= a.t.n_pts) return;
+  const int e1 = a.t.begin[p + 1];
+  for (int e = a.t.begin[p]; e < e1; e++) {
+    const uint32_t v = a.t.obs[e];
+    if (v >> 31) continue;
+    const int r = (int)((v >> 13) & 4095u);
+    if (r >= a.t.n_live || r == self) continue;
+    if (a.culled && a.culled[r]) continue;
+    const int orow = a.row_at_idrank[r], os = (int)(v & 8191u);
+    if ((unsigned)orow >= (unsigned)a.M || os >= a.t.S || os >= a.t.row_n[orow]) continue;
+    int32_t* cell = a.t.rows + (size_t)orow * a.t.S + os;
+    if (*cell == p) *cell = -1;
+  }
+}
+
+// grid n - start: candidate start + blockIdx.x
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_cull_eval(CovisCullArgs a) {
+  __shared__ int s_mps[COVIS_ROW_THREADS / 64], s_red[COVIS_ROW_THREADS / 64];
+  const int c = a.start + (int)blockIdx.x, tid = threadIdx.x;
+  if (c >= a.n) return;
+  const int flag = a.cand_flag[c];
+  if (flag & 2) {
+    if (tid == 0) {
+      a.decision[c] = CULL_SKIPPED;
+      a.n_mps[c] = 0;
+      a.n_red[c] = 0;
+    }
+    return;
+  }
+  const int row = a.cand_row[c];
+  if ((unsigned)row >= (unsigned)a.M) return;
+  const int len = min(max(a.t.row_n[row], 0), a.t.S);
+  const int self = a.id_rank_of_row[row];
+  const size_t base = (size_t)row * a.t.S;
+  int mps = 0, red = 0;
+  for (int i = tid; i < len; i += COVIS_ROW_THREADS) {
+    const int p = a.t.rows[base + i];
+    if ((unsigned)p >= (unsigned)a.t.n_pts) continue;
+    const uint8_t at = a.attr[base + i];
+    if (!cull_slot_counted(p, a.t.bad[p], at, a.monocular)) continue;
+    mps++;
+    int obs, gated, self_slot;
+    covis_cull_walk(a, p, self, at, &obs, &gated, &self_slot);
+    if (cull_slot_redundant(obs, gated)) red++;
+  }
+  mps = wave_sum(mps);
+  red = wave_sum(red);
+  if (lane_id() == 0) {
+    s_mps[wave_id()] = mps;
+    s_red[wave_id()] = red;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int m = 0, r = 0;
+    for (int w = 0; w < COVIS_ROW_THREADS / 64; w++) {
+      m += s_mps[w];
+      r += s_red[w];
+    }
+    const int d = cull_decision(r, m, flag & 1);
+    a.decision[c] = (uint8_t)d;
+    a.n_mps[c] = m;
+    a.n_red[c] = r;
+    if (d == CULL_CULLED) atomicMin(a.round_min, c);
+  }
+}
+
+// One workgroup. EraseObservation(this) on every first-occurrence slot of the culled row in slot order
+// (the list order comes from the block scan), then the row leaves the table.
+__global__ __launch_bounds__(COVIS_THREADS) void k_covis_cull_commit(CovisCullArgs a) {
+  __shared__ int s_wsum[COVIS_THREADS / 64];
+  const int c = *a.round_min, tid = threadIdx.x;
+  if (c < 0 || c >= a.n) return;  // nobody culls: the call is decided
+  const int row = a.cand_row[c];
+  if ((unsigned)row >= (unsigned)a.M) return;
+  const int len = min(max(a.t.row_n[row], 0), a.t.S);
+  const int self = a.id_rank_of_row[row];
+  const size_t base = (size_t)row * a.t.S;
+  const int cursor = *a.bad_cursor;
+  __syncthreads();  // row_n[row] and the cursor are rewritten below
+  int run = 0;
+  for (int chunk = 0; chunk < len; chunk += 4 * COVIS_THREADS) {
+    int v[4], pt[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int i = chunk + tid * 4 + j;
+      v[j] = 0;
+      pt[j] = -1;
+      if (i >= len) continue;
+      const int p = a.t.rows[base + i];
+      if ((unsigned)p >= (unsigned)a.t.n_pts) continue;
+      if (a.t.bad[p]) continue;  // its observations are gone already
+      int obs, gated, self_slot;
+      covis_cull_walk(a, p, self, 0, &obs, &gated, &self_slot);
+      if (self_slot != i) continue;  // held in a lower slot too: erased there
+      const uint8_t own = a.attr[base + i];
+      if (cull_point_goes_bad(obs - cull_weight(own))) {
+        v[j] = 1;
+        pt[j] = p;
+      }
+    }
+    __syncthreads();  // every flag of the chunk was read before one is written
+    const int total = covis_block_scan4(v, s_wsum);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (pt[j] < 0) continue;
+      const int at = cursor + run + v[j];
+      if (at < a.bad_cap) a.bad_list[at] = pt[j];
+      covis_cull_set_bad(a, pt[j], self);
+    }
+    run += total;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    a.culled[self] = 1;
+    a.t.row_n[row] = -1;
+    a.bad_count[c] = run;
+    *a.bad_cursor = cursor + run;
+  }
+}
+
+struct CovisCullPointsArgs {
+  CovisCullArgs a;  // the table part; culled = NULL
+  int n_points;
+  const int32_t* ids;
+  const int32_t* found;
+  const int32_t* visible;
+  const long long* first;
+  long long current;
+  uint8_t* action;
+  int P;
+};
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_cull_points(CovisCullPointsArgs q) {
+  const int i = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (i >= q.n_points) return;
+  const int p = q.ids[i];
+  if ((unsigned)p >= (unsigned)q.P) return;
+  int obs = 0, gated, self_slot;
+  if (p < q.a.t.n_pts) covis_cull_walk(q.a, p, -1, 0, &obs, &gated, &self_slot);
+  const int act = cull_point_action(q.a.t.bad[p], q.found[i], q.visible[i], q.current, q.first[i], obs, q.a.monocular);
+  q.action[i] = (uint8_t)act;
+  if (act == CULL_PT_RATIO || act == CULL_PT_OBS) covis_cull_set_bad(q.a, p, -1);
+}
+
 // ------------------------------------------------------------------------------------------
 // host
 
@@ -415,6 +616,9 @@ struct orbfe_covis {
   uint8_t* d_is_local = nullptr;         // [M]
   int32_t* d_seen = nullptr;             // [M]
   int32_t* d_order = nullptr;            // [M]
+  uint8_t* d_attr = nullptr;             // [M * S] one attribute byte per row slot
+  int32_t* d_row_at_idrank = nullptr;    // [M]
+  int32_t* d_culled = nullptr;           // [M] by mnId rank: culled in this call
   unsigned long long* d_tmp = nullptr;   // [obs_cap]
   uint32_t* d_obs = nullptr;             // [obs_cap]
   long long obs_cap = 0;
@@ -528,6 +732,10 @@ extern "C" int orbfe_covis_create(int device, int max_keyframes, int max_slots, 
   COVIS_TRY(hipMalloc((void**)&h->d_is_local, M));
   COVIS_TRY(hipMalloc((void**)&h->d_seen, 4 * M));
   COVIS_TRY(hipMalloc((void**)&h->d_order, 4 * M));
+  COVIS_TRY(hipMalloc((void**)&h->d_attr, M * S));
+  COVIS_TRY(hipMalloc((void**)&h->d_row_at_idrank, 4 * M));
+  COVIS_TRY(hipMalloc((void**)&h->d_culled, 4 * M));
+  COVIS_TRY(hipMemsetAsync(h->d_row_at_idrank, 0, 4 * M, h->stream));
   COVIS_TRY(hipMemsetAsync(h->d_row_n, 0xff, 4 * M, h->stream));
   COVIS_TRY(hipMemsetAsync(h->d_bad, 0, P, h->stream));
   COVIS_TRY(hipMemsetAsync(h->d_a, 0, 4 * (P + 1), h->stream));
@@ -556,6 +764,9 @@ extern "C" int orbfe_covis_destroy(orbfe_covis* h) {
     hipFree(h->d_is_local);
     hipFree(h->d_seen);
     hipFree(h->d_order);
+    hipFree(h->d_attr);
+    hipFree(h->d_row_at_idrank);
+    hipFree(h->d_culled);
     hipFree(h->d_tmp);
     hipFree(h->d_obs);
     hipFree(h->d_stage);
@@ -695,7 +906,7 @@ static CovisTable covis_table(const orbfe_covis* h) {
 }
 
 static size_t covis_refresh_bytes(const orbfe_covis* h) {
-  return covis_al(4 * (size_t)h->core.M) + covis_al(2 * (size_t)h->core.M);
+  return 2 * covis_al(4 * (size_t)h->core.M) + covis_al(2 * (size_t)h->core.M);
 }
 
 static int covis_max_row(const orbfe_covis* h) {
@@ -712,6 +923,8 @@ static int covis_refresh(orbfe_covis* h) {
     int st = covis_upload(h, c.id_rank_of_row.data(), 4 * c.id_rank_of_row.size(), h->d_id_rank_of_row, nullptr);
     if (st) return st;
     st = covis_upload(h, c.tie_rank_of_id_rank.data(), 2 * c.tie_rank_of_id_rank.size(), h->d_tie_of_idrank, nullptr);
+    if (st) return st;
+    st = covis_upload(h, c.row_at_id_rank.data(), 4 * c.row_at_id_rank.size(), h->d_row_at_idrank, nullptr);
     if (st) return st;
     c.stale = true;  // inverse entries carry mnId ranks
   }
@@ -987,5 +1200,194 @@ extern "C" int orbfe_covis_local_map(orbfe_covis* h, int n_local, const int64_t*
     memcpy(r->edge_kf, hres + o_ekf, 4 * (size_t)ne);
     memcpy(r->edge_slot, hres + o_esl, 4 * (size_t)ne);
   }
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_set_keyframe_attrs(orbfe_covis* h, int64_t kf_id, int n_slots, const uint8_t* attrs) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_keyframe_attrs: bad argument");
+  int row = -1;
+  cc::Status cs = h->core.prepare_attrs(kf_id, n_slots, attrs, &row);
+  if (cs) return covis_fail("orbfe_covis_set_keyframe_attrs", cs);
+  if (h->device >= 0 && n_slots > 0) {
+    hipSetDevice(h->device);
+    int st = covis_stage_reserve(h, covis_al((size_t)n_slots));
+    if (st) return st;
+    st = covis_upload(h, attrs, (size_t)n_slots, h->d_attr + (size_t)row * h->core.S, nullptr);
+    if (st) return st;
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  }
+  h->core.commit_attrs(row);
+  return ORBFE_OK;
+}
+
+static CovisCullArgs covis_cull_args(const orbfe_covis* h) {
+  CovisCullArgs a;
+  memset(&a, 0, sizeof(a));
+  a.t = covis_table(h);
+  a.M = h->core.M;
+  a.attr = h->d_attr;
+  a.row_at_idrank = h->d_row_at_idrank;
+  a.id_rank_of_row = h->d_id_rank_of_row;
+  return a;
+}
+
+extern "C" int orbfe_covis_cull_keyframes(orbfe_covis* h, int n, const int64_t* kf_ids, const uint8_t* not_erase,
+                                          int monocular, orbfe_covis_cull_t* r) {
+  if (!h || !r || !r->bad_begin || r->bad_capacity < 0 || (r->bad_capacity > 0 && !r->bad_points) ||
+      (n > 0 && (!r->decision || !r->n_mps || !r->n_redundant)))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_cull_keyframes: bad argument");
+  cc::Status cs = h->core.prepare_cull(n, kf_ids, not_erase, r->bad_capacity, &h->tmp_rows);
+  if (cs) return covis_fail("orbfe_covis_cull_keyframes", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "covisibility table is host-only (device < 0)");
+  r->bad_begin[0] = 0;
+  if (n == 0) return ORBFE_OK;
+  hipSetDevice(h->device);
+  cc::Core& c = h->core;
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + covis_al(4 * (size_t)n) + covis_al((size_t)n));
+  if (st) return st;
+  st = covis_refresh(h);
+  if (st) return st;
+  std::vector<uint8_t> flag(n);
+  int64_t need = 0;
+  for (int i = 0; i < n; i++) {
+    flag[i] = (uint8_t)((not_erase[i] ? 1 : 0) | (kf_ids[i] == 0 ? 2 : 0));
+    need += c.row_n[h->tmp_rows[i]];
+  }
+  const void *d_rows, *d_flag;
+  st = covis_upload(h, h->tmp_rows.data(), 4 * (size_t)n, nullptr, &d_rows);
+  if (st) return st;
+  st = covis_upload(h, flag.data(), (size_t)n, nullptr, &d_flag);
+  if (st) return st;
+  // result words: round_min[n + 1] | cursor | n_mps[n] | n_red[n] | bad_count[n] | bad_list[need] ; decision[n] bytes
+  const size_t o_cur = (size_t)n + 1, o_mps = o_cur + 1, o_red = o_mps + n, o_cnt = o_red + n, o_list = o_cnt + n,
+               o_dec = o_list + (size_t)need, bytes = 4 * o_dec + (size_t)n;
+  st = covis_res_reserve(h, bytes);
+  if (st) return st;
+  int32_t* d = reinterpret_cast<int32_t*>(h->d_res);
+  int32_t* hres = reinterpret_cast<int32_t*>(h->h_res);
+  ORBFE_HIP_CHECK(hipMemsetAsync(d, 0x7f, 4 * ((size_t)n + 1), h->stream));
+  ORBFE_HIP_CHECK(hipMemsetAsync(d + o_cur, 0, bytes - 4 * o_cur, h->stream));
+  ORBFE_HIP_CHECK(hipMemsetAsync(h->d_culled, 0, 4 * (size_t)c.M, h->stream));
+  CovisCullArgs a = covis_cull_args(h);
+  a.culled = h->d_culled;
+  a.cand_row = (const int32_t*)d_rows;
+  a.cand_flag = (const uint8_t*)d_flag;
+  a.n = n;
+  a.monocular = monocular ? 1 : 0;
+  a.decision = reinterpret_cast<uint8_t*>(d + o_dec);
+  a.n_mps = d + o_mps;
+  a.n_red = d + o_red;
+  a.bad_count = d + o_cnt;
+  a.bad_list = d + o_list;
+  a.bad_cursor = d + o_cur;
+  a.bad_cap = (int)need;
+  std::vector<int> culled;
+  int start = 0;
+  // A round decides every candidate from `start` on against the culls so far; the lowest one that culls is
+  // committed and the next round starts behind it. Rounds = culls + 1 at the most.
+  for (int round = 0; round <= n && start < n; round++) {
+    a.start = start;
+    a.round_min = d + round;
+    ORBFE_LAUNCH("k_covis_cull_eval", k_covis_cull_eval, dim3(n - start), dim3(COVIS_ROW_THREADS), 0, h->stream, a);
+    ORBFE_LAUNCH("k_covis_cull_commit", k_covis_cull_commit, dim3(1), dim3(COVIS_THREADS), 0, h->stream, a);
+    ORBFE_HIP_CHECK(hipGetLastError());
+    ORBFE_HIP_CHECK(hipMemcpyAsync(hres + round, d + round, 4, hipMemcpyDeviceToHost, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    const int idx = hres[round];
+    if (idx == COVIS_CULL_NONE) break;
+    if (idx < start || idx >= n) {
+      c.stale = true;
+      return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_cull_keyframes: corrupt result");
+    }
+    culled.push_back(idx);
+    start = idx + 1;
+  }
+  ORBFE_HIP_CHECK(hipMemcpyAsync(hres + o_cur, d + o_cur, bytes - 4 * o_cur, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  // the table changed whatever follows
+  for (int idx : culled) {
+    int row = -1;
+    c.erase(kf_ids[idx], &row);
+  }
+  bool sane = hres[o_cur] >= 0 && hres[o_cur] <= need;
+  int64_t total = 0;
+  for (int i = 0; sane && i < n; i++) {
+    const int k = hres[o_cnt + i];
+    sane = k >= 0 && total + k <= need;
+    total += k;
+  }
+  sane = sane && total == hres[o_cur];
+  for (int64_t i = 0; sane && i < total; i++) sane = hres[o_list + i] >= 0 && hres[o_list + i] < c.P;
+  if (!sane) {
+    c.stale = true;
+    return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_cull_keyframes: corrupt result");
+  }
+  if (total > 0) c.stale = true;
+  const uint8_t* dec = reinterpret_cast<const uint8_t*>(hres + o_dec);
+  int32_t at = 0;
+  for (int i = 0; i < n; i++) {
+    r->decision[i] = dec[i];
+    r->n_mps[i] = hres[o_mps + i];
+    r->n_redundant[i] = hres[o_red + i];
+    r->bad_begin[i] = at;
+    at += hres[o_cnt + i];
+  }
+  r->bad_begin[n] = at;
+  if (total > 0) memcpy(r->bad_points, hres + o_list, 4 * (size_t)total);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_cull_points(orbfe_covis* h, int n, const int32_t* point_ids, const int32_t* found,
+                                       const int32_t* visible, const int64_t* first_kf_id, int64_t current_kf_id,
+                                       int monocular, uint8_t* action) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_cull_points: bad argument");
+  cc::Status cs = h->core.prepare_cull_points(n, point_ids, found, visible, first_kf_id, current_kf_id, action);
+  if (cs) return covis_fail("orbfe_covis_cull_points", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "covisibility table is host-only (device < 0)");
+  if (n == 0) return ORBFE_OK;
+  hipSetDevice(h->device);
+  cc::Core& c = h->core;
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + 3 * covis_al(4 * (size_t)n) + covis_al(8 * (size_t)n));
+  if (st) return st;
+  st = covis_refresh(h);
+  if (st) return st;
+  const void *d_ids, *d_found, *d_vis, *d_first;
+  st = covis_upload(h, point_ids, 4 * (size_t)n, nullptr, &d_ids);
+  if (st) return st;
+  st = covis_upload(h, found, 4 * (size_t)n, nullptr, &d_found);
+  if (st) return st;
+  st = covis_upload(h, visible, 4 * (size_t)n, nullptr, &d_vis);
+  if (st) return st;
+  st = covis_upload(h, first_kf_id, 8 * (size_t)n, nullptr, &d_first);
+  if (st) return st;
+  st = covis_res_reserve(h, (size_t)n);
+  if (st) return st;
+  CovisCullPointsArgs q;
+  q.a = covis_cull_args(h);
+  q.a.monocular = monocular ? 1 : 0;
+  q.n_points = n;
+  q.ids = (const int32_t*)d_ids;
+  q.found = (const int32_t*)d_found;
+  q.visible = (const int32_t*)d_vis;
+  q.first = (const long long*)d_first;
+  q.current = current_kf_id;
+  q.action = h->d_res;
+  q.P = c.P;
+  ORBFE_HIP_CHECK(hipMemsetAsync(h->d_res, 0xff, (size_t)n, h->stream));
+  ORBFE_LAUNCH("k_covis_cull_points", k_covis_cull_points, dim3((n + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS),
+               dim3(COVIS_ROW_THREADS), 0, h->stream, q);
+  ORBFE_HIP_CHECK(hipGetLastError());
+  ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  bool changed = false;
+  for (int i = 0; i < n; i++) {
+    if (h->h_res[i] > CULL_PT_AGE) {
+      c.stale = true;
+      return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_cull_points: corrupt result");
+    }
+    changed = changed || h->h_res[i] == CULL_PT_RATIO || h->h_res[i] == CULL_PT_OBS;
+  }
+  if (changed) c.stale = true;
+  memcpy(action, h->h_res, (size_t)n);
   return ORBFE_OK;
 }

@@ -35,6 +35,8 @@ struct Core {
   std::vector<uint64_t> key_of;              // [M]
   std::vector<uint8_t> live;                 // [M]
   std::vector<int32_t> row_n;                // [M] slots of the row
+  std::vector<uint8_t> has_attr;             // [M] the row's per-slot attributes are stored
+  int n_attr = 0;                            // live rows with attributes
   std::priority_queue<int, std::vector<int>, std::greater<int>> free_rows;  // below hi
   int hi = 0;               // rows ever used
   int64_t total_slots = 0;  // sum of row_n over live rows: bounds the inverse's entries
@@ -69,6 +71,8 @@ struct Core {
     key_of.assign(M, 0);
     live.assign(M, 0);
     row_n.assign(M, -1);
+    has_attr.assign(M, 0);
+    n_attr = 0;
     free_rows = {};
     hi = 0;
     total_slots = 0;
@@ -122,6 +126,7 @@ struct Core {
       ranks_dirty = true;
     } else {
       total_slots -= row_n[row];
+      if (row_n[row] != n_slots) drop_attrs(row);  // other keypoints
       if (key_of[row] != tie_key) {
         slot_of_key.erase(key_of[row]);
         key_of[row] = tie_key;
@@ -175,11 +180,66 @@ struct Core {
     slot_of.erase(it);
     slot_of_key.erase(key_of[r]);
     live[r] = 0;
+    drop_attrs(r);
     total_slots -= row_n[r];
     row_n[r] = -1;
     free_rows.push(r);
     stale = true;
     ranks_dirty = true;
+    return ok();
+  }
+
+  void drop_attrs(int row) {
+    if (has_attr[row]) n_attr--;
+    has_attr[row] = 0;
+  }
+
+  // Checks of set_keyframe_attrs
+  Status prepare_attrs(int64_t kf_id, int n_slots, const uint8_t* attrs, int* row) const {
+    if (n_slots < 0 || (n_slots > 0 && !attrs)) return {ERR_ARG, "bad argument"};
+    auto it = slot_of.find(kf_id);
+    if (it == slot_of.end()) return {ERR_STATE, "keyframe id not stored"};
+    if (n_slots != row_n[it->second]) return {ERR_ARG, "n_slots differs from the stored row's length"};
+    for (int i = 0; i < n_slots; i++)
+      if (attrs[i] & 0x80) return {ERR_ARG, "bit 7 of an attribute byte is set"};
+    *row = it->second;
+    return ok();
+  }
+
+  void commit_attrs(int row) {
+    if (!has_attr[row]) n_attr++;
+    has_attr[row] = 1;
+  }
+
+  bool all_have_attrs() const { return n_attr == size(); }
+
+  // Checks of cull_keyframes: the candidates' rows, and the bound on the bad list.
+  Status prepare_cull(int n, const int64_t* kf_ids, const uint8_t* not_erase, int bad_capacity,
+                      std::vector<int32_t>* rows) const {
+    if (n > 0 && !not_erase) return {ERR_ARG, "bad argument"};
+    Status st = local_rows(n, kf_ids, rows);
+    if (st) return st;
+    if (!all_have_attrs()) return {ERR_STATE, "a stored keyframe has no attributes"};
+    int64_t need = 0;
+    for (int i = 0; i < n; i++) need += row_n[(*rows)[i]];
+    if (bad_capacity < need) return {ERR_CAPACITY, "bad_capacity below the sum of the candidates' row lengths"};
+    return ok();
+  }
+
+  // Checks of cull_points
+  Status prepare_cull_points(int n, const int32_t* ids, const int32_t* found, const int32_t* visible,
+                             const int64_t* first_kf_id, int64_t current_kf_id, const uint8_t* action) const {
+    if (n < 0 || (n > 0 && (!ids || !found || !visible || !first_kf_id || !action))) return {ERR_ARG, "bad argument"};
+    const int64_t lim = (int64_t)1 << 31;
+    if (current_kf_id < 0 || current_kf_id >= lim) return {ERR_ARG, "a keyframe id outside 0 .. 2^31 - 1"};
+    std::vector<int32_t> s(ids, ids + n);
+    for (int i = 0; i < n; i++) {
+      if (ids[i] < 0 || ids[i] >= P) return {ERR_ARG, "a point id outside 0 .. max_point_id - 1"};
+      if (first_kf_id[i] < 0 || first_kf_id[i] >= lim) return {ERR_ARG, "a keyframe id outside 0 .. 2^31 - 1"};
+    }
+    std::sort(s.begin(), s.end());
+    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return {ERR_ARG, "a point named twice"};
+    if (!all_have_attrs()) return {ERR_STATE, "a stored keyframe has no attributes"};
     return ok();
   }
 
