@@ -11,7 +11,7 @@ from .covisibility import CovisibilityGraph
 from .essential_graph import EssentialGraphOptimizer, OptimizeEssentialGraph, problem_of_essential_graph
 from .extractor import ORBextractor, register_host, synth_frame, synth_sequence_frame, unregister_host
 from .frames import (DeviceTriKeyFrame, FeatureVector, Frame, KeyFrame, KeyFrameMapPoints, LastFrameMapPoints,
-                     LocalMapPoints, MapPointGeometry, TriKeyFrame)
+                     LocalMapPoints, MapPointGeometry, ResidentLocalMap, TriKeyFrame)
 from .initializer import Initializer, InitializerBatch
 from .keyframe_database import KeyFrameDatabase, SharingList
 from .global_bundle_adjustment import GlobalBundleAdjuster, GlobalBundleAdjustment, problem_of_map
@@ -26,5 +26,5 @@ from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
 __all__ = ["ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "CovisibilityGraph", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "Initializer", "InitializerBatch", "PoseOptimizer", "PoseOptimization", "Sim3Optimizer", "OptimizeSim3", "problem_of_keyframes", "LocalBundleAdjuster", "LocalBundleAdjustment", "problem_of_local_map", "GlobalBundleAdjuster", "GlobalBundleAdjustment", "problem_of_map", "EssentialGraphOptimizer", "OptimizeEssentialGraph", "problem_of_essential_graph", "MapCorrector", "UpdateNormalAndDepth", "CorrectLoopPoses", "ApplyGlobalBundleAdjustment", "normals_problem_of_map", "loop_problem_of_map", "gba_update_problem_of_map", "Frame", "KeyFrame",
            "TriKeyFrame", "DeviceTriKeyFrame",
-           "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
+           "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "ResidentLocalMap", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

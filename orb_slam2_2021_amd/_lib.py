@@ -1,7 +1,7 @@
 """ctypes binding of liborbfe.so (include/orbfe.h, orbfe_match_batch.h, orbfe_debug.h, orbfe_synth.h,
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
-orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h,
+orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h, orbfe_localmap.h,
 orbfe_mapcorr.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
@@ -139,6 +139,15 @@ class covis_local_map(Structure):
 class covis_cull(Structure):
     _fields_ = [("decision", c_void_p), ("n_mps", c_void_p), ("n_redundant", c_void_p), ("bad_begin", c_void_p),
                 ("bad_points", c_void_p), ("bad_capacity", c_int)]
+
+
+class covis_points(Structure):  # orbfe_localmap.h
+    _fields_ = [("point_capacity", c_int), ("n_points", c_int), ("point_ids", c_void_p)]
+
+
+class covis_local_geometry(Structure):
+    _fields_ = [("point_capacity", c_int), ("n_points", c_int), ("n_missing", c_int), ("point_ids", c_void_p),
+                ("geometry", mappoint_geometry)]
 
 
 class sim3_solver(Structure):  # orbfe_sim3.h
@@ -575,6 +584,12 @@ _SIGNATURES = {
     "orbfe_covis_cull_keyframes": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(covis_cull)]),
     "orbfe_covis_cull_points": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64,
                                         c_int, c_void_p]),
+    # orbfe_localmap.h
+    "orbfe_covis_distinct_points": (c_int, [c_void_p, c_int, c_void_p, POINTER(covis_points)]),
+    "orbfe_covis_set_point_geometry": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_void_p]),
+    "orbfe_covis_local_geometry": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                           POINTER(covis_local_geometry)]),
     # orbfe_poseopt.h
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),

@@ -10,6 +10,12 @@ keyframe by keyframe. LocalMapping::KeyFrameCulling and MapPointCulling run over
 (keyframe_culling, map_point_culling); what KeyFrame::SetBadFlag does to the graph and the spanning
 tree is applied here (set_bad_flag). Keyframes are named by mnId; every order among equal weights is the tie
 key's (the reference's KeyFrame* value; mnId unless given).
+
+The local map (include/orbfe_localmap.h): distinct_points is the walk of Tracking::UpdateLocalPoints,
+SearchInNeighbors' vpFuseCandidates and ComputeSim3's mvpLoopMapPoints on the device; set_point_geometry feeds the
+per-point store and local_geometry gathers the walk's points from it into a ResidentLocalMap that stays in HBM;
+update_local_keyframes adds the host half of Tracking::UpdateLocalKeyFrames (Tracking.cc:1306-1365) to the vote, and
+update_local_map runs them for one Frame.
 """
 from __future__ import annotations
 
@@ -20,6 +26,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple
 import numpy as np
 
 from . import _lib as L
+from .frames import ResidentLocalMap
 
 
 class _Node:
@@ -46,6 +53,9 @@ class CovisibilityGraph:
                                              byref(h)), "orbfe_covis_create")
         self._h = h
         self._max_slots = int(max_slots)
+        self._max_point_id = int(max_point_id)
+        self._local_generation = 0  # local_geometry calls so far: a ResidentLocalMap of an earlier one is stale
+        self._pt_buf = np.zeros(65536, np.int32)
         self._kfdb = kfdb
         self._nodes: Dict[int, _Node] = {}
 
@@ -326,6 +336,148 @@ class CovisibilityGraph:
         return SimpleNamespace(point_ids=pts[:r.n_points].copy(), fixed_ids=fixed[:r.n_fixed].copy(),
                                edge_begin=ebeg[:r.n_points + 1].copy(), edge_kf=ekf[:r.n_edges].copy(),
                                edge_slot=esl[:r.n_edges].copy())
+
+    # ---- the local map (include/orbfe_localmap.h) ------------------------------------------------
+    def _point_buffer(self, need: int) -> np.ndarray:
+        if need > len(self._pt_buf):
+            self._pt_buf = np.zeros(max(need, 2 * len(self._pt_buf)), np.int32)
+        return self._pt_buf
+
+    def distinct_points(self, kf_ids: Iterable[int]) -> np.ndarray:
+        """orbfe_covis_distinct_points: the non-bad points in the rows of kf_ids (repeats allowed), each once, in
+        first-occurrence order over (list position, slot) -- the reference's push_back order at Tracking.cc:1228-1252,
+        LocalMapping.cc:500-521 and LoopClosing.cc:371-391. An empty list gives an empty result."""
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        if len(ids) == 0:
+            return np.zeros(0, np.int32)
+        for _ in range(2):
+            buf = self._pt_buf
+            r = L.covis_points(point_capacity=len(buf), n_points=0, point_ids=L.ptr(buf))
+            st = self._lib.orbfe_covis_distinct_points(self._h, len(ids), L.ptr(ids), byref(r))
+            if st == L.ORBFE_ERR_CAPACITY and r.n_points > len(buf):
+                self._point_buffer(r.n_points)
+                continue
+            break
+        L.check(st, "orbfe_covis_distinct_points")
+        return buf[:r.n_points].copy()
+
+    def set_point_geometry(self, point_ids, world_pos, normal, min_distance, max_distance, descriptors,
+                           flags=0) -> None:
+        """Creates or overwrites the stored geometry of the given points (SetWorldPos, UpdateNormalAndDepth,
+        ComputeDistinctiveDescriptors as the caller mirrors them). flags: the bits handed on with each point
+        (MPF_OBSERVED, ...), one per point or one for all; MPF_BAD, MPF_SEEN and MPF_TRACK_IN_VIEW are refused."""
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        n = len(p)
+        f = np.ascontiguousarray(np.broadcast_to(np.asarray(flags, np.uint8), (n,)))
+        wp = np.ascontiguousarray(world_pos, np.float32).reshape(n, 3)
+        nr = np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+        mn = np.ascontiguousarray(min_distance, np.float32).reshape(n)
+        mx = np.ascontiguousarray(max_distance, np.float32).reshape(n)
+        d = np.ascontiguousarray(descriptors, np.uint8).reshape(n, 32)
+        L.check(self._lib.orbfe_covis_set_point_geometry(self._h, n, L.ptr(p), L.ptr(f), L.ptr(wp), L.ptr(nr),
+                                                         L.ptr(mn), L.ptr(mx), L.ptr(d)),
+                "orbfe_covis_set_point_geometry")
+
+    def local_geometry(self, kf_ids: Iterable[int], seen_point_ids=()) -> Tuple[np.ndarray, ResidentLocalMap]:
+        """orbfe_covis_local_geometry: distinct_points(kf_ids) and, gathered on the device from the store, the
+        MapPointGeometry of those points with MPF_SEEN on the ones in seen_point_ids (the Frame's mvpMapPoints; -1
+        and bad points skipped). Returns (point_ids, ResidentLocalMap); entry i of the map is point_ids[i]. Earlier
+        ResidentLocalMaps of this graph become stale. A point whose geometry was never set: OrbfeError with status
+        ORBFE_ERR_STATE and the attribute n_missing."""
+        ids = np.ascontiguousarray(list(kf_ids), np.int64)
+        seen = np.ascontiguousarray(seen_point_ids, np.int32).reshape(-1)
+        self._local_generation += 1
+        if len(ids) == 0:
+            return np.zeros(0, np.int32), ResidentLocalMap(self, self._local_generation, L.mappoint_geometry())
+        for _ in range(2):
+            buf = self._pt_buf
+            r = L.covis_local_geometry(point_capacity=len(buf), point_ids=L.ptr(buf))
+            st = self._lib.orbfe_covis_local_geometry(self._h, len(ids), L.ptr(ids), len(seen), L.ptr(seen),
+                                                      byref(r))
+            if st == L.ORBFE_ERR_CAPACITY and r.n_points > len(buf):
+                self._point_buffer(r.n_points)
+                continue
+            break
+        if st < 0:
+            e = L.OrbfeError(st, "orbfe_covis_local_geometry")
+            e.n_missing = int(r.n_missing)
+            raise e
+        return buf[:r.n_points].copy(), ResidentLocalMap(self, self._local_generation, r.geometry)
+
+    def update_local_keyframes(self, frame_point_ids) -> Optional[Tuple[List[int], int]]:
+        """Tracking::UpdateLocalKeyFrames (Tracking.cc:1254-1366) for a Frame given as its mvpMapPoints: the vote on
+        the device, then :1306-1365 on the host from the graph state. Returns (local_kf_ids in mvpLocalKeyFrames'
+        order, reference_kf = pKFmax), or None when nothing was voted (:1277-1278: the caller keeps its lists).
+        The loop runs over the voted keyframes only (itEndKF is taken before the pushes); the > 80 test comes first in
+        each turn; per turn the first not-yet-included of GetBestCovisibilityKeyFrames(10), then the first
+        not-yet-included child in tie-key order (set<KeyFrame*>), then the parent, whose break (:1355) ends the whole
+        loop. Bad keyframes are in neither the table nor the graph, so the reference's isBad() tests are vacuous
+        here; a parent id that erase() left dangling is passed over like a NULL parent."""
+        v = self.vote([frame_point_ids])[0]
+        if not v.kf_ids:
+            return None
+        local = list(v.kf_ids)
+        included = set(local)  # mnTrackReferenceForFrame == mCurrentFrame.mnId
+        for kf in v.kf_ids:
+            if len(local) > 80:
+                break
+            node = self._nodes[kf]
+            for nb in node.ordered[:10]:
+                if nb in self._nodes and nb not in included:
+                    local.append(nb)
+                    included.add(nb)
+                    break
+            for ch in sorted(node.children, key=self._tie):
+                if ch in self._nodes and ch not in included:
+                    local.append(ch)
+                    included.add(ch)
+                    break
+            par = node.parent
+            if par is not None and par in self._nodes and par not in included:
+                local.append(par)
+                included.add(par)
+                break
+        return local, v.kf_max
+
+    def update_local_map(self, frame_point_ids) -> Optional[SimpleNamespace]:
+        """Tracking::UpdateLocalMap for one Frame (its mvpMapPoints as point ids): update_local_keyframes, then
+        UpdateLocalPoints with the geometry (local_geometry, the Frame's own points marked MPF_SEEN). Returns
+        local_kf_ids, reference_kf, point_ids and local_map (a ResidentLocalMap for ORBmatcher.SearchLocalPoints), or
+        None when nothing was voted."""
+        r = self.update_local_keyframes(frame_point_ids)
+        if r is None:
+            return None
+        point_ids, local_map = self.local_geometry(r[0], frame_point_ids)
+        return SimpleNamespace(local_kf_ids=r[0], reference_kf=r[1], point_ids=point_ids, local_map=local_map)
+
+    def fuse_targets(self, kf_id: int, monocular: bool) -> List[int]:
+        """vpTargetKFs of LocalMapping::SearchInNeighbors (LocalMapping.cc:463-486): the best 20 (monocular) or 10
+        neighbours, each followed by its own best 5 that are neither stamped nor the keyframe itself. Second
+        neighbours are not stamped (mnFuseTargetForKF is set at :473 only), so one can appear more than once: the
+        repeats are kept."""
+        kf_id = int(kf_id)
+        targets: List[int] = []
+        stamped: Set[int] = set()
+        for k in self.GetBestCovisibilityKeyFrames(kf_id, 20 if monocular else 10):
+            if k not in self._nodes or k in stamped:
+                continue
+            targets.append(k)
+            stamped.add(k)
+            for k2 in self.GetBestCovisibilityKeyFrames(k, 5):
+                if k2 not in self._nodes or k2 in stamped or k2 == kf_id:
+                    continue
+                targets.append(k2)
+        return targets
+
+    def fuse_candidates(self, kf_id: int, monocular: bool) -> np.ndarray:
+        """vpFuseCandidates (LocalMapping.cc:500-521): distinct_points over fuse_targets."""
+        return self.distinct_points(self.fuse_targets(kf_id, monocular))
+
+    def loop_map_points(self, matched_kf_id: int) -> np.ndarray:
+        """mvpLoopMapPoints (LoopClosing.cc:372-391): distinct_points over the matched keyframe's
+        GetVectorCovisibleKeyFrames() followed by the keyframe itself."""
+        k = int(matched_kf_id)
+        return self.distinct_points(self.GetVectorCovisibleKeyFrames(k) + [k])
 
     # ---- the reference's side effects ----------------------------------------------------------
     def _update_best_covisibles(self, node: _Node) -> None:

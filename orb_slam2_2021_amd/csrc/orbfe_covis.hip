@@ -26,6 +26,8 @@
 // Local map: k_covis_lm_mark (points of the local rows) -> k_covis_lm_count (edges per marked
 // point) -> two scans -> k_covis_lm_emit (points, CSR, raw edges, seen keyframes) ->
 // k_covis_lm_order (one workgroup: local then fixed, both ascending in mnId rank) -> k_covis_lm_edges.
+// The ordered distinct union of rows and the geometry store (include/orbfe_localmap.h) are at the end of
+// the file: k_lm_first -> k_lm_count -> scan -> k_lm_emit -> (k_lm_gather, k_lm_seen) -> k_lm_reset.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,12 +37,15 @@
 
 #include "../../include/orbfe.h"
 #include "../../include/orbfe_covis.h"
+#include "../../include/orbfe_localmap.h"
 #include "orbfe_covis_core.h"
 #include "orbfe_cull_core.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_localmap_core.h"
 
 namespace cc = orbfe_covis_core;
+namespace lm = orbfe_localmap_core;
 
 #define COVIS_THREADS 1024
 #define COVIS_BINS 4096       // = ORBFE_COVIS_MAX_KEYFRAMES = 4 per thread
@@ -629,6 +634,13 @@ struct orbfe_covis {
   uint8_t* d_res = nullptr;
   size_t res_cap = 0;
   std::vector<int32_t> tmp_rows, tmp_slots, tmp_ids;
+  // include/orbfe_localmap.h, each allocated on first use
+  uint32_t* d_lm_first = nullptr;  // [P] all ones between calls
+  bool lm_dirty = false;           // a call was cut short: d_lm_first is refilled whole by the next one
+  uint8_t* d_geo_rec = nullptr;    // [P * 64] the geometry store
+  uint8_t* d_geo_state = nullptr;  // [P] stored flags | lm::kPresent
+  uint8_t* d_geo_out = nullptr;    // the gathered SoA of one call: 65 bytes per point, geo_out_cap points
+  int geo_out_cap = 0;
 };
 
 static size_t covis_al(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -771,6 +783,10 @@ extern "C" int orbfe_covis_destroy(orbfe_covis* h) {
     hipFree(h->d_obs);
     hipFree(h->d_stage);
     hipFree(h->d_res);
+    hipFree(h->d_lm_first);
+    hipFree(h->d_geo_rec);
+    hipFree(h->d_geo_state);
+    hipFree(h->d_geo_out);
     if (h->h_stage) hipHostFree(h->h_stage);
     if (h->h_res) hipHostFree(h->h_res);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -868,6 +884,7 @@ extern "C" int orbfe_covis_clear(orbfe_covis* h) {
     hipSetDevice(h->device);
     ORBFE_HIP_CHECK(hipMemsetAsync(h->d_row_n, 0xff, 4 * (size_t)h->core.M, h->stream));
     ORBFE_HIP_CHECK(hipMemsetAsync(h->d_bad, 0, (size_t)h->core.P, h->stream));
+    if (h->d_geo_state) ORBFE_HIP_CHECK(hipMemsetAsync(h->d_geo_state, 0, (size_t)h->core.P, h->stream));
     ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
   }
   h->core.clear();
@@ -1389,5 +1406,384 @@ extern "C" int orbfe_covis_cull_points(orbfe_covis* h, int n, const int32_t* poi
   }
   if (changed) c.stale = true;
   memcpy(action, h->h_res, (size_t)n);
+  return ORBFE_OK;
+}
+
+// ---- the local map (include/orbfe_localmap.h; orbfe_localmap_core.h holds the index arithmetic) ----
+// The three row passes run one thread per (list position, slot) on a grid (nbx, n_kf) of 256 threads, so
+// workgroup lm_block(position, bx) covers 256 consecutive slots and the workgroups ascend in (position,
+// slot): k_lm_first takes the minimum key per point, k_lm_count counts each workgroup's first occurrences,
+// the scan kernels above turn the counts into offsets, k_lm_emit ranks the first occurrences inside the
+// workgroup (ballot + four wave totals), writes the point at offset + rank and the tagged index back into
+// first[p]. k_lm_gather: four lanes per result point, one 16-byte load and store each of the 64-byte
+// record. k_lm_seen: one thread per entry of the Frame's list. k_lm_reset: first[p] over the result only.
+// Guards: a list row against M, a slot against the row's length and S, a point id against P (first, bad,
+// the store and its state all hold P entries), an output index against `bound` (the capacity of out and of
+// the gathered arrays), a result index against hdr[0] and bound.
+struct LmArgs {
+  const int32_t* rows;       // [M * S]
+  const int32_t* row_n;      // [M]
+  const uint8_t* bad;        // [P]
+  int M, S, P;
+  const int32_t* list_rows;  // [n_kf] row per list position
+  int n_kf, nbx, n_blocks;
+  uint32_t* first;           // [P]
+  int32_t* blk;              // [n_blocks + 1]
+  int32_t* hdr;              // {n_points, n_missing, 0, 0}
+  int32_t* out;              // [bound]
+  int bound;
+};
+
+// the non-bad point in slot s of list position pos, or -1
+__device__ __forceinline__ int lm_slot_point(const LmArgs& a, int pos, int s) {
+  const int k = a.list_rows[pos];
+  if ((unsigned)k >= (unsigned)a.M) return -1;
+  if (s >= a.row_n[k] || s >= a.S) return -1;
+  const int p = a.rows[(size_t)k * a.S + s];
+  if ((unsigned)p >= (unsigned)a.P) return -1;
+  return a.bad[p] ? -1 : p;
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_first(LmArgs a) {
+  const int pos = blockIdx.y, s = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  const int p = lm_slot_point(a, pos, s);
+  if (p >= 0) atomicMin(&a.first[p], lm::lm_key(pos, s));
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_count(LmArgs a) {
+  __shared__ int s_w[COVIS_ROW_THREADS / 64];
+  const int pos = blockIdx.y, s = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  const int p = lm_slot_point(a, pos, s);
+  const bool win = p >= 0 && a.first[p] == lm::lm_key(pos, s);
+  const uint64_t m = wave_ballot(win);
+  if (lane_id() == 0) s_w[wave_id()] = __popcll(m);
+  __syncthreads();
+  const int b = lm::lm_block(pos, blockIdx.x, a.nbx);
+  if (threadIdx.x == 0 && b < a.n_blocks) a.blk[b] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_emit(LmArgs a) {
+  __shared__ int s_w[COVIS_ROW_THREADS / 64];
+  const int pos = blockIdx.y, s = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  const int p = lm_slot_point(a, pos, s);
+  const bool win = p >= 0 && a.first[p] == lm::lm_key(pos, s);
+  const uint64_t m = wave_ballot(win);
+  const int w = wave_id();
+  if (lane_id() == 0) s_w[w] = __popcll(m);
+  __syncthreads();
+  const int b = lm::lm_block(pos, blockIdx.x, a.nbx);
+  if (b == 0 && threadIdx.x == 0) a.hdr[0] = a.blk[a.n_blocks];
+  if (!win || b >= a.n_blocks) return;
+  int off = a.blk[b];
+  for (int k = 0; k < COVIS_ROW_THREADS / 64; k++) off += k < w ? s_w[k] : 0;
+  const int idx = off + prefix_in_wave(m);
+  if ((unsigned)idx >= (unsigned)a.bound) return;
+  a.out[idx] = p;
+  a.first[p] = lm::lm_tag(idx);  // equals no key: every other thread of p still loses
+}
+
+struct LmGatherArgs {
+  const int32_t* hdr;    // hdr[0] = n_points
+  int32_t* missing;      // hdr + 1
+  const int32_t* out;    // [bound]
+  int bound, P;
+  const uint4* rec;      // [P * 4]
+  const uint8_t* state;  // [P]
+  uint4* desc;           // [bound * 2]
+  uint32_t* pos;         // [bound * 3] float bits
+  uint32_t* nrm;         // [bound * 3]
+  uint32_t* min_d;       // [bound]
+  uint32_t* max_d;       // [bound]
+  uint8_t* flags;        // [bound]
+};
+
+// grid ceil(4 * bound / 256): lanes 4i .. 4i+3 move point i; 0, 1 the descriptor halves, 2, 3 the floats
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_gather(LmGatherArgs g) {
+  const long long t = (long long)blockIdx.x * COVIS_ROW_THREADS + threadIdx.x;
+  const int i = (int)(t >> 2), q = (int)(t & 3);
+  if (i >= g.bound || i >= g.hdr[0]) return;
+  const int p = g.out[i];
+  if ((unsigned)p >= (unsigned)g.P) return;
+  const uint8_t st = g.state[p];
+  if (!(st & lm::kPresent)) {
+    if (q == 0) atomicAdd(g.missing, 1);
+    return;
+  }
+  const uint4 v = g.rec[(size_t)p * 4 + q];
+  if (q < 2) {
+    g.desc[(size_t)i * 2 + q] = v;
+    if (q == 0) g.flags[i] = (uint8_t)(st & ~lm::kPresent);
+  } else if (q == 2) {
+    g.pos[3 * (size_t)i] = v.x;
+    g.pos[3 * (size_t)i + 1] = v.y;
+    g.pos[3 * (size_t)i + 2] = v.z;
+    g.nrm[3 * (size_t)i] = v.w;
+  } else {
+    g.nrm[3 * (size_t)i + 1] = v.x;
+    g.nrm[3 * (size_t)i + 2] = v.y;
+    g.min_d[i] = v.z;
+    g.max_d[i] = v.w;
+  }
+}
+
+// After the gather: the whole flag byte of a seen point is stored again with ORBFE_MPF_SEEN, so a point
+// listed twice is written twice with the same value.
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_seen(LmGatherArgs g, const uint32_t* first, int n_seen,
+                                                               const int32_t* seen) {
+  const int j = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (j >= n_seen) return;
+  const int p = seen[j];
+  if ((unsigned)p >= (unsigned)g.P) return;  // -1: no point
+  const uint32_t v = first[p];
+  if (!lm::lm_is_index(v)) return;  // bad, or in no named row
+  const int idx = lm::lm_index(v);
+  if (idx >= g.bound || idx >= g.hdr[0]) return;
+  g.flags[idx] = (uint8_t)((g.state[p] & ~lm::kPresent) | ORBFE_MPF_SEEN);
+}
+
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_reset(LmArgs a) {
+  const int i = (int)(blockIdx.x * COVIS_ROW_THREADS + threadIdx.x);
+  if (i >= a.bound || i >= a.hdr[0]) return;
+  const int p = a.out[i];
+  if ((unsigned)p < (unsigned)a.P) a.first[p] = lm::kNone;
+}
+
+// grid ceil(4 * n / 256): the records of one staging pass into the store
+__global__ __launch_bounds__(COVIS_ROW_THREADS) void k_lm_set_geometry(int n, const int32_t* ids, const uint8_t* flags,
+                                                                       const uint4* src, int P, uint4* rec,
+                                                                       uint8_t* state) {
+  const long long t = (long long)blockIdx.x * COVIS_ROW_THREADS + threadIdx.x;
+  const int i = (int)(t >> 2), q = (int)(t & 3);
+  if (i >= n) return;
+  const int p = ids[i];
+  if ((unsigned)p >= (unsigned)P) return;
+  rec[(size_t)p * 4 + q] = src[(size_t)i * 4 + q];
+  if (q == 0) state[p] = (uint8_t)(flags[i] | lm::kPresent);
+}
+
+static const char* const kHostOnly = "covisibility table is host-only (device < 0)";
+
+// The gathered SoA of `cap` points inside d_geo_out (cap a multiple of 64: every array 256-byte aligned).
+static void covis_lm_geo_view(const orbfe_covis* h, LmGatherArgs* g) {
+  const size_t cap = (size_t)h->geo_out_cap;
+  uint8_t* b = h->d_geo_out;
+  g->desc = reinterpret_cast<uint4*>(b);
+  g->pos = reinterpret_cast<uint32_t*>(b + 32 * cap);
+  g->nrm = reinterpret_cast<uint32_t*>(b + 44 * cap);
+  g->min_d = reinterpret_cast<uint32_t*>(b + 56 * cap);
+  g->max_d = reinterpret_cast<uint32_t*>(b + 60 * cap);
+  g->flags = b + 64 * cap;
+}
+
+// The whole device pass for the list in h->tmp_rows. On return the stream is idle, h_res[0..1] hold
+// n_points and n_missing, the ids are in d_res at word *ids_at.
+static int covis_lm_run(orbfe_covis* h, const lm::Plan& plan, int n_kf, int n_seen, const int32_t* seen, bool gather,
+                        int* n_points, int* n_missing, size_t* ids_at) {
+  const cc::Core& c = h->core;
+  *n_points = *n_missing = 0;
+  *ids_at = 0;
+  hipSetDevice(h->device);
+  if (!h->d_lm_first) {
+    ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_lm_first, 4 * (size_t)c.P));
+    h->lm_dirty = true;
+  }
+  if (h->lm_dirty) {
+    ORBFE_HIP_CHECK(hipMemsetAsync(h->d_lm_first, 0xff, 4 * (size_t)c.P, h->stream));
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->lm_dirty = false;
+  }
+  if (plan.max_row == 0 || plan.bound == 0) return ORBFE_OK;  // every named row is empty
+  int st = covis_stage_reserve(h, covis_al(4 * (size_t)n_kf) + covis_al(4 * (size_t)n_seen));
+  if (st) return st;
+  const size_t o_blk = 4, o_out = o_blk + (size_t)plan.n_blocks + 1, words = o_out + (size_t)plan.bound;
+  st = covis_res_reserve(h, 4 * words);
+  if (st) return st;
+  if (gather && plan.bound > h->geo_out_cap) {
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    const long long want = std::max<long long>(plan.bound, (long long)h->geo_out_cap * 2);
+    const int cap = (int)std::min<long long>((want + 63) & ~63ll, ((long long)c.P + 63) & ~63ll);
+    hipFree(h->d_geo_out);
+    h->d_geo_out = nullptr;
+    h->geo_out_cap = 0;
+    ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_geo_out, 65 * (size_t)cap));
+    h->geo_out_cap = cap;
+  }
+  const void *d_list, *d_seen = nullptr;
+  st = covis_upload(h, h->tmp_rows.data(), 4 * (size_t)n_kf, nullptr, &d_list);
+  if (st) return st;
+  if (gather && n_seen > 0) {
+    st = covis_upload(h, seen, 4 * (size_t)n_seen, nullptr, &d_seen);
+    if (st) return st;
+  }
+  int32_t* d = reinterpret_cast<int32_t*>(h->d_res);
+  LmArgs a;
+  a.rows = h->d_rows;
+  a.row_n = h->d_row_n;
+  a.bad = h->d_bad;
+  a.M = c.M;
+  a.S = c.S;
+  a.P = c.P;
+  a.list_rows = (const int32_t*)d_list;
+  a.n_kf = n_kf;
+  a.nbx = plan.nbx;
+  a.n_blocks = plan.n_blocks;
+  a.first = h->d_lm_first;
+  a.hdr = d;
+  a.blk = d + o_blk;
+  a.out = d + o_out;
+  a.bound = plan.bound;
+  const dim3 grid(plan.nbx, n_kf), block(COVIS_ROW_THREADS);
+  const unsigned rb = (unsigned)((plan.bound + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS);
+  h->lm_dirty = true;  // until the reset below has run
+  ORBFE_HIP_CHECK(hipMemsetAsync(d, 0, 16, h->stream));
+  ORBFE_LAUNCH("k_lm_first", k_lm_first, grid, block, 0, h->stream, a);
+  ORBFE_LAUNCH("k_lm_count", k_lm_count, grid, block, 0, h->stream, a);
+  covis_scan(h, a.blk, plan.n_blocks);
+  ORBFE_LAUNCH("k_lm_emit", k_lm_emit, grid, block, 0, h->stream, a);
+  if (gather) {
+    LmGatherArgs g;
+    g.hdr = d;
+    g.missing = d + 1;
+    g.out = a.out;
+    g.bound = plan.bound;
+    g.P = c.P;
+    g.rec = reinterpret_cast<const uint4*>(h->d_geo_rec);
+    g.state = h->d_geo_state;
+    covis_lm_geo_view(h, &g);
+    const unsigned gb = (unsigned)((4ll * plan.bound + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS);
+    ORBFE_LAUNCH("k_lm_gather", k_lm_gather, dim3(gb), block, 0, h->stream, g);
+    if (n_seen > 0)
+      ORBFE_LAUNCH("k_lm_seen", k_lm_seen, dim3((n_seen + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS), block, 0,
+                   h->stream, g, (const uint32_t*)h->d_lm_first, n_seen, (const int32_t*)d_seen);
+  }
+  ORBFE_LAUNCH("k_lm_reset", k_lm_reset, dim3(rb), block, 0, h->stream, a);
+  ORBFE_HIP_CHECK(hipGetLastError());
+  ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, d, 16, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  h->lm_dirty = false;
+  const int32_t* hres = reinterpret_cast<const int32_t*>(h->h_res);
+  if (hres[0] < 0 || hres[0] > plan.bound || hres[1] < 0 || hres[1] > hres[0])
+    return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_distinct_points: corrupt result");
+  *n_points = hres[0];
+  *n_missing = hres[1];
+  *ids_at = o_out;
+  return ORBFE_OK;
+}
+
+// n ids from word `at` of d_res to the caller
+static int covis_lm_ids(orbfe_covis* h, size_t at, int n, int32_t* dst) {
+  if (n == 0) return ORBFE_OK;
+  ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res + 4 * at, h->d_res + 4 * at, 4 * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  memcpy(dst, h->h_res + 4 * at, 4 * (size_t)n);
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_distinct_points(orbfe_covis* h, int n_kf, const int64_t* kf_ids, orbfe_covis_points_t* r) {
+  if (!h || !r || r->point_capacity < 0 || (r->point_capacity > 0 && !r->point_ids))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_distinct_points: bad argument");
+  lm::Plan plan;
+  cc::Status cs = lm::check_list(h->core, n_kf, kf_ids, &h->tmp_rows, &plan);
+  if (cs) return covis_fail("orbfe_covis_distinct_points", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, kHostOnly);
+  int np = 0, nm = 0;
+  size_t at = 0;
+  int st = covis_lm_run(h, plan, n_kf, 0, nullptr, false, &np, &nm, &at);
+  if (st) return st;
+  r->n_points = np;
+  if (np > r->point_capacity)
+    return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_covis_distinct_points: point_capacity below the result");
+  return covis_lm_ids(h, at, np, r->point_ids);
+}
+
+extern "C" int orbfe_covis_set_point_geometry(orbfe_covis* h, int n, const int32_t* point_ids, const uint8_t* flags,
+                                              const float* world_pos, const float* normal, const float* min_distance,
+                                              const float* max_distance, const uint8_t* descriptors) {
+  if (!h) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_point_geometry: bad argument");
+  cc::Status cs = lm::check_geometry(h->core, n, point_ids, flags, world_pos, normal, min_distance, max_distance,
+                                     descriptors);
+  if (cs) return covis_fail("orbfe_covis_set_point_geometry", cs);
+  if (h->device < 0 || n == 0) return ORBFE_OK;
+  hipSetDevice(h->device);
+  const size_t P = (size_t)h->core.P;
+  if (!h->d_geo_rec) {
+    uint8_t *rec = nullptr, *state = nullptr;
+    ORBFE_HIP_CHECK(hipMalloc((void**)&rec, lm::kRecord * P));
+    hipError_t e = hipMalloc((void**)&state, P);
+    if (e == hipSuccess) e = hipMemsetAsync(state, 0, P, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+      hipFree(rec);
+      hipFree(state);
+      return orbfe_set_hip_error(e, "orbfe_covis_set_point_geometry: the store");
+    }
+    h->d_geo_rec = rec;
+    h->d_geo_state = state;
+  }
+  for (int b = 0; b < n; b += lm::kSetChunk) {
+    const int m = std::min(lm::kSetChunk, n - b);
+    int st = covis_stage_reserve(h, covis_al(lm::kRecord * (size_t)m) + covis_al(4 * (size_t)m) + covis_al((size_t)m));
+    if (st) return st;
+    const size_t off = covis_stage_take(h, lm::kRecord * (size_t)m);
+    for (int i = 0; i < m; i++)
+      lm::pack_record(h->h_stage + off + lm::kRecord * (size_t)i, b + i, world_pos, normal, min_distance, max_distance,
+                      descriptors);
+    ORBFE_HIP_CHECK(hipMemcpyAsync(h->d_stage + off, h->h_stage + off, lm::kRecord * (size_t)m, hipMemcpyHostToDevice,
+                                   h->stream));
+    const void *d_ids, *d_flags;
+    st = covis_upload(h, point_ids + b, 4 * (size_t)m, nullptr, &d_ids);
+    if (st) return st;
+    st = covis_upload(h, flags + b, (size_t)m, nullptr, &d_flags);
+    if (st) return st;
+    ORBFE_LAUNCH("k_lm_set_geometry", k_lm_set_geometry,
+                 dim3((unsigned)((4ll * m + COVIS_ROW_THREADS - 1) / COVIS_ROW_THREADS)), dim3(COVIS_ROW_THREADS), 0,
+                 h->stream, m, (const int32_t*)d_ids, (const uint8_t*)d_flags,
+                 reinterpret_cast<const uint4*>(h->d_stage + off), h->core.P, reinterpret_cast<uint4*>(h->d_geo_rec),
+                 h->d_geo_state);
+    ORBFE_HIP_CHECK(hipGetLastError());
+    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));  // the next pass reuses the staging
+  }
+  return ORBFE_OK;
+}
+
+extern "C" int orbfe_covis_local_geometry(orbfe_covis* h, int n_kf, const int64_t* kf_ids, int n_seen,
+                                          const int32_t* seen_point_ids, orbfe_covis_local_geometry_t* r) {
+  if (!h || !r || r->point_capacity < 0 || (r->point_capacity > 0 && !r->point_ids))
+    return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_local_geometry: bad argument");
+  lm::Plan plan;
+  cc::Status cs = lm::check_list(h->core, n_kf, kf_ids, &h->tmp_rows, &plan);
+  if (cs) return covis_fail("orbfe_covis_local_geometry", cs);
+  cs = lm::check_seen(h->core, n_seen, seen_point_ids);
+  if (cs) return covis_fail("orbfe_covis_local_geometry", cs);
+  if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, kHostOnly);
+  r->n_points = r->n_missing = 0;
+  memset(&r->geometry, 0, sizeof(r->geometry));
+  int np = 0, nm = 0;
+  size_t at = 0;
+  int st;
+  if (!h->d_geo_rec) {  // an empty store: every point of the list is missing
+    st = covis_lm_run(h, plan, n_kf, 0, nullptr, false, &np, &nm, &at);
+    nm = np;
+  } else {
+    st = covis_lm_run(h, plan, n_kf, n_seen, seen_point_ids, true, &np, &nm, &at);
+  }
+  if (st) return st;
+  r->n_points = np;
+  r->n_missing = nm;
+  if (np > r->point_capacity)
+    return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_covis_local_geometry: point_capacity below the result");
+  st = covis_lm_ids(h, at, np, r->point_ids);
+  if (st) return st;
+  if (nm > 0) return orbfe_set_error(ORBFE_ERR_STATE, "orbfe_covis_local_geometry: a point's geometry was never set");
+  if (np == 0) return ORBFE_OK;
+  LmGatherArgs g;
+  covis_lm_geo_view(h, &g);
+  r->geometry.m = np;
+  r->geometry.flags = g.flags;
+  r->geometry.world_pos = reinterpret_cast<const float*>(g.pos);
+  r->geometry.normal = reinterpret_cast<const float*>(g.nrm);
+  r->geometry.min_distance = reinterpret_cast<const float*>(g.min_d);
+  r->geometry.max_distance = reinterpret_cast<const float*>(g.max_d);
+  r->geometry.descriptors = reinterpret_cast<const uint8_t*>(g.desc);
   return ORBFE_OK;
 }

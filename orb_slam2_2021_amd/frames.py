@@ -361,6 +361,72 @@ class DeviceMapPointGeometry:
         return v
 
 
+class _DeviceBytes:
+    """A device address inside a buffer somebody else owns, where a resident map's descriptors are expected
+    (LocalMapPoints keeps them on the device; _lib.ptr takes data_ptr())."""
+
+    is_cuda = True
+
+    def __init__(self, address: int, owner):
+        self._address = int(address)
+        self._owner = owner
+
+    def data_ptr(self) -> int:
+        self._owner._check()
+        return self._address
+
+
+class ResidentLocalMap:
+    """The local map as CovisibilityGraph.local_geometry leaves it in HBM (include/orbfe_localmap.h): an
+    orbfe_mappoint_geometry of device pointers into buffers the graph's handle owns. ORBmatcher.SearchLocalPoints
+    and isInFrustum take it wherever they take a DeviceMapPointGeometry. The next local_geometry call on the
+    graph reuses the buffers: using this object after it raises RuntimeError."""
+
+    def __init__(self, graph, generation: int, geometry: L.mappoint_geometry):
+        self._graph = graph
+        self._generation = int(generation)
+        self._geometry = geometry
+        self.m = int(geometry.m)
+        self.descriptors = _DeviceBytes(geometry.descriptors or 0, self)
+
+    def _check(self) -> None:
+        if self._graph._local_generation != self._generation or self._graph._h is None:
+            raise RuntimeError("this ResidentLocalMap is stale: the graph's local_geometry ran again (or the graph "
+                               "was closed) and its buffers were reused")
+
+    def __len__(self) -> int:
+        return self.m
+
+    def view(self) -> L.mappoint_geometry:
+        self._check()
+        v = L.mappoint_geometry()
+        v.m = self.m
+        for f in DeviceMapPointGeometry.FIELDS:
+            setattr(v, f, getattr(self._geometry, f))
+        return v
+
+    def to_host(self) -> "MapPointGeometry":
+        """The six arrays copied to the host (tests and debugging; the searches never need it)."""
+        import ctypes
+        self._check()
+        m = self.m
+        sizes = {"flags": (np.uint8, (m,)), "world_pos": (np.float32, (m, 3)), "normal": (np.float32, (m, 3)),
+                 "min_distance": (np.float32, (m,)), "max_distance": (np.float32, (m,)),
+                 "descriptors": (np.uint8, (m, 32))}
+        hip_memcpy = L.lib().hipMemcpy  # the HIP runtime liborbfe.so is linked against
+        hip_memcpy.restype = ctypes.c_int
+        hip_memcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        out = {}
+        for f, (dt, shape) in sizes.items():
+            a = np.zeros(shape, dt)
+            if a.nbytes:
+                e = hip_memcpy(L.ptr(a), L.ptr(getattr(self._geometry, f) or 0), a.nbytes, 2)  # device to host
+                if e != 0:
+                    raise RuntimeError(f"hipMemcpy of {f} failed with HIP error {e}")
+            out[f] = a
+        return MapPointGeometry(**out)
+
+
 @dataclass
 class KeyFrameMapPoints:
     """pKF->GetMapPointMatches() by KeyFrame keypoint with the KeyFrame's mvKeysUn angles, as
