@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "orbfe.h"
+#include "orbfe_frame.h"
 #include "orbfe_keyframe.h"
 #include "orbfe_stereo.h"
 
@@ -292,6 +293,69 @@ inline void ComputeStereoMatches(Extractor& left, Extractor& right, const std::v
   check(orbfe_compute_stereo_matches(left.handle(), 0, right.handle(), 0, kl.data(), dl.data(), (int)kl.size(),
                                      kr.data(), dr.data(), (int)kr.size(), mbf, mb, uRight.data(), depth.data()),
         "orbfe_compute_stereo_matches");
+}
+
+// ---- the monocular and RGB-D Frames (include/orbfe_frame.h) -------------------------------------
+using Camera = orbfe_camera;  // mK, mDistCoef (4 or 5 entries) and mbf
+
+// What the RGB-D / monocular constructors leave in a Frame (Frame.cc:154-277): mvKeys, mDescriptors,
+// mvKeysUn, mvuRight, mvDepth and the image bounds {mnMinX, mnMaxX, mnMinY, mnMaxY}.
+struct SensorFrame {
+  std::vector<KeyPoint> keys, keysUn;
+  std::vector<uint8_t> descriptors;
+  std::vector<float> uRight, depth;
+  float bounds[4] = {0.f, 0.f, 0.f, 0.f};
+};
+
+// Frame::ComputeImageBounds (Frame.cc:488-520).
+inline void ImageBounds(const Camera& cam, int rows, int cols, float out[4]) {
+  check(orbfe_image_bounds(&cam, rows, cols, out), "orbfe_image_bounds");
+}
+// Frame::UndistortKeyPoints (Frame.cc:456-486) on host arrays.
+inline void UndistortKeyPoints(const Camera& cam, const std::vector<KeyPoint>& keys, std::vector<KeyPoint>& keysUn) {
+  keysUn.resize(keys.size());
+  check(orbfe_undistort_keypoints_host(&cam, keys.data(), (int)keys.size(), keysUn.data()),
+        "orbfe_undistort_keypoints_host");
+}
+// Frame::ComputeStereoFromRGBD (Frame.cc:702-723) on host arrays; depthMap is the raw map (NULL: monocular).
+inline void StereoFromDepth(const Camera& cam, const std::vector<KeyPoint>& keys, const std::vector<KeyPoint>& keysUn,
+                            const void* depthMap, size_t depthStep, int depthType, float depthFactor, int rows,
+                            int cols, std::vector<float>& uRight, std::vector<float>& depth) {
+  uRight.assign(keys.size(), -1.0f);
+  depth.assign(keys.size(), -1.0f);
+  check(orbfe_stereo_from_depth_host(&cam, keys.data(), keysUn.data(), (int)keys.size(), depthMap, depthStep,
+                                     depthType, depthFactor, rows, cols, uRight.data(), depth.data()),
+        "orbfe_stereo_from_depth_host");
+}
+
+// The RGB-D Frame (depthMap != NULL) or the monocular Frame (depthMap == NULL) in one blocking call: image of
+// 1, 3 or 4 channels in host memory; channel 0 is R when rgb (mbRGB).
+inline void MakeSensorFrame(Extractor& e, const uint8_t* image, int rows, int cols, size_t step, int channels,
+                            bool rgb, const Camera& cam, SensorFrame& out, const void* depthMap = nullptr,
+                            size_t depthStep = 0, int depthType = ORBFE_DEPTH_F32, float depthFactor = 1.0f,
+                            int grayMode = ORBFE_GRAY_SHIFT15) {
+  ImageBounds(cam, rows, cols, out.bounds);
+  const int cap = rows > 0 && cols > 0 ? check(orbfe_max_keypoints(e.handle(), rows, cols), "orbfe_max_keypoints") : 1;
+  out.keys.resize(cap);
+  out.keysUn.resize(cap);
+  out.descriptors.resize((size_t)cap * ORBFE_DESC_BYTES);
+  out.uRight.resize(cap);
+  out.depth.resize(cap);
+  int n = 0;
+  if (depthMap)
+    check(orbfe_rgbd_frame(e.handle(), image, rows, cols, step, channels, rgb ? 1 : 0, grayMode, depthMap, depthStep,
+                           depthType, depthFactor, &cam, out.keys.data(), out.descriptors.data(), &n, cap,
+                           out.keysUn.data(), out.uRight.data(), out.depth.data()),
+          "orbfe_rgbd_frame");
+  else
+    check(orbfe_mono_frame(e.handle(), image, rows, cols, step, channels, rgb ? 1 : 0, grayMode, &cam, out.keys.data(),
+                           out.descriptors.data(), &n, cap, out.keysUn.data(), out.uRight.data(), out.depth.data()),
+          "orbfe_mono_frame");
+  out.keys.resize(n);
+  out.keysUn.resize(n);
+  out.descriptors.resize((size_t)n * ORBFE_DESC_BYTES);
+  out.uRight.resize(n);
+  out.depth.resize(n);
 }
 
 }  // namespace orbfe

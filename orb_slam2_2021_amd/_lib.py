@@ -2,7 +2,7 @@
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
 orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h, orbfe_localmap.h,
-orbfe_mapcorr.h).
+orbfe_mapcorr.h, orbfe_frame.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -386,6 +386,26 @@ TRI_REJ_DIST_ZERO, TRI_REJ_SCALE, TRI_REJ_UNPROJECT, TRI_REJ_BAD_MATCH, TRI_REJ_
 TRI_MAX_KEYS, TRI_MAX_KF2_KEYS, TRI_MAX_PAIRS, TRI_MAX_NEIGHBOURS = 8192, 16384, 4096, 64
 
 
+GRAY_SHIFT15, GRAY_SHIFT14 = 0, 1  # orbfe_frame.h: cvtColor's 4.x / 2.4-3.x tables
+DEPTH_U16, DEPTH_F32 = 0, 1
+
+
+class camera(Structure):  # orbfe_frame.h
+    _fields_ = [("fx", c_float), ("fy", c_float), ("cx", c_float), ("cy", c_float), ("dist", c_float * 5),
+                ("n_dist", c_int32), ("bf", c_float)]
+
+
+def make_camera(fx, fy, cx, cy, dist, bf) -> camera:
+    """mK, mDistCoef (k1, k2, p1, p2[, k3]) and mbf as an orbfe_camera."""
+    d = [float(v) for v in np.asarray(dist, np.float32).reshape(-1)]
+    if len(d) not in (4, 5):
+        raise ValueError("mDistCoef has 4 or 5 entries")
+    c = camera(fx=float(fx), fy=float(fy), cx=float(cx), cy=float(cy), n_dist=len(d), bf=float(bf))
+    for i, v in enumerate(d):
+        c.dist[i] = v
+    return c
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "orbfe_last_error": (c_char_p, []),
@@ -496,6 +516,21 @@ _SIGNATURES = {
     "orbfe_stereo_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_float,
                                    c_float, c_void_p, c_void_p, POINTER(c_int), c_void_p, c_void_p,
                                    POINTER(c_int), c_int, c_void_p, c_void_p]),
+    # orbfe_frame.h
+    "orbfe_image_bounds": (c_int, [POINTER(camera), c_int, c_int, c_void_p]),
+    "orbfe_gray_batch_device": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_size_t, c_int, c_int, c_int, c_int,
+                                        c_int, c_void_p, c_size_t, c_size_t, c_void_p]),
+    "orbfe_frame_finish_batch_device": (c_int, [c_void_p, c_int, POINTER(camera), c_void_p, c_void_p, c_int,
+                                                c_void_p, c_size_t, c_size_t, c_int, c_float, c_int, c_int,
+                                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "orbfe_undistort_keypoints_host": (c_int, [POINTER(camera), c_void_p, c_int, c_void_p]),
+    "orbfe_stereo_from_depth_host": (c_int, [POINTER(camera), c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_int,
+                                             c_float, c_int, c_int, c_void_p, c_void_p]),
+    "orbfe_mono_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_int, c_int, c_int, POINTER(camera),
+                                 c_void_p, c_void_p, POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
+    "orbfe_rgbd_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_int, c_int, c_int, c_void_p,
+                                 c_size_t, c_int, c_float, POINTER(camera), c_void_p, c_void_p, POINTER(c_int),
+                                 c_int, c_void_p, c_void_p, c_void_p]),
     "orbfe_is_in_frustum": (c_int, [c_void_p, POINTER(frame_view), POINTER(mappoint_geometry),
                                     c_void_p, c_float, c_float, POINTER(frustum_out),
                                     POINTER(c_int)]),

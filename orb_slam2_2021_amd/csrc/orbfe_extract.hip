@@ -2551,6 +2551,8 @@ struct orbfe_extractor {
   bool hpyr_pending = false;
   // Frame::ComputeStereoMatches scratch (orbfe_stereo.hip)
   OrbfeStereoScratch* stereo = nullptr;
+  // the monocular / RGB-D Frames' staging buffers (orbfe_frame.hip)
+  OrbfeFrameScratch* frame = nullptr;
   // launch_extract's enqueue sequence captured once per distinct set of arguments and replayed as
   // a hipGraph (orbfe_extractor_set_graphs; `graphs` keyed by everything the sequence depends on).
   // Off by default: measured slower on MI355X / ROCm 7.2
@@ -3476,6 +3478,7 @@ extern "C" int orbfe_extractor_destroy(orbfe_extractor* h) {
   if (h->h2d) hipStreamSynchronize(h->h2d);
   if (h->d2h) hipStreamSynchronize(h->d2h);  // (the host-pyramid prefetch reads d_pyr)
   orbfe_internal_stereo_free(h->stereo);
+  orbfe_internal_frame_free(h->frame);
   drop_graphs(h);
   free_batch(h);
   hipFree(h->d_levels);
@@ -4057,6 +4060,11 @@ int orbfe_internal_pyramid(orbfe_extractor* h, OrbfePyramid* out) {
 }
 
 OrbfeStereoScratch** orbfe_internal_stereo_slot(orbfe_extractor* h) { return &h->stereo; }
+OrbfeFrameScratch** orbfe_internal_frame_slot(orbfe_extractor* h) { return &h->frame; }
+int orbfe_internal_device(orbfe_extractor* h, hipStream_t* stream) {
+  *stream = h->stream;
+  return h->device;
+}
 
 extern "C" int orbfe_get_level(orbfe_extractor* h, int image, int level, const uint8_t** p,
                                int* rows, int* cols, size_t* step) {

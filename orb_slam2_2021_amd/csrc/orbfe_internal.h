@@ -43,3 +43,12 @@ int orbfe_internal_extract_batch(orbfe_extractor* h, int n, const uint8_t* const
 struct OrbfeStereoScratch;
 OrbfeStereoScratch** orbfe_internal_stereo_slot(orbfe_extractor* h);
 void orbfe_internal_stereo_free(OrbfeStereoScratch* s);
+
+// The device and the stream of a handle (valid before any extract call, unlike orbfe_internal_pyramid).
+int orbfe_internal_device(orbfe_extractor* h, hipStream_t* stream);
+
+// Staging buffers of the monocular / RGB-D Frames owned by the handle (created lazily by
+// orbfe_frame.hip, freed with the handle).
+struct OrbfeFrameScratch;
+OrbfeFrameScratch** orbfe_internal_frame_slot(orbfe_extractor* h);
+void orbfe_internal_frame_free(OrbfeFrameScratch* s);

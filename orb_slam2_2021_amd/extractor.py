@@ -207,6 +207,97 @@ class ORBextractor:
         return (kl[:a].copy(), dl[:a].copy() if a else None, kr[:b].copy(),
                 dr[:b].copy() if b else None, ur[:a].copy(), dep[:a].copy())
 
+    # ---- the monocular and RGB-D Frames (src/Frame.cc:154-277; include/orbfe_frame.h) --------
+    def _sensor_frame(self, image, camera, depth_map, depth_factor, rgb, gray_mode):
+        from .frames import Frame
+        img = np.asarray(image)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3, 4)):
+            raise ValueError("a CV_8UC1, CV_8UC3 or CV_8UC4 image is expected")  # Tracking.cc:229-244
+        img = np.ascontiguousarray(img)
+        rows, cols = img.shape[:2]
+        channels = 1 if img.ndim == 2 else img.shape[2]
+        cam = camera if isinstance(camera, L.camera) else L.make_camera(**camera)
+        bounds = np.zeros(4, np.float32)
+        L.check(self._lib.orbfe_image_bounds(byref(cam), rows, cols, L.ptr(bounds)), "orbfe_image_bounds")
+        cap = self.max_keypoints(rows, cols) if img.size else 1
+        kps = np.zeros(cap, L.KEYPOINT_DTYPE)
+        un = np.zeros(cap, L.KEYPOINT_DTYPE)
+        desc = np.zeros((cap, 32), np.uint8)
+        ur = np.zeros(cap, np.float32)
+        dep = np.zeros(cap, np.float32)
+        n = c_int()
+        step = c_size_t(img.strides[0] if img.size else cols * channels)
+        if depth_map is None:
+            L.check(self._lib.orbfe_mono_frame(self._h, L.ptr(img), rows, cols, step, channels, int(bool(rgb)),
+                                               int(gray_mode), byref(cam), L.ptr(kps), L.ptr(desc), byref(n), cap,
+                                               L.ptr(un), L.ptr(ur), L.ptr(dep)), "orbfe_mono_frame")
+        else:
+            dm = np.asarray(depth_map)
+            if dm.dtype not in (np.uint16, np.float32) or dm.shape != (rows, cols):
+                raise ValueError("the depth map is uint16 or float32 and has the image's shape")
+            dm = np.ascontiguousarray(dm)
+            dtype = L.DEPTH_U16 if dm.dtype == np.uint16 else L.DEPTH_F32
+            L.check(self._lib.orbfe_rgbd_frame(self._h, L.ptr(img), rows, cols, step, channels, int(bool(rgb)),
+                                               int(gray_mode), L.ptr(dm), c_size_t(dm.strides[0]), dtype,
+                                               float(depth_factor), byref(cam), L.ptr(kps), L.ptr(desc), byref(n),
+                                               cap, L.ptr(un), L.ptr(ur), L.ptr(dep)), "orbfe_rgbd_frame")
+        if img.size:
+            self._last_shape = (rows, cols)
+        k = n.value
+        return Frame(keys_un=un[:k].copy(), descriptors=desc[:k].copy(), u_right=ur[:k].copy(),
+                     mp_state=np.zeros(k, np.uint8), scale_factors=self._scale.copy(), level_sigma2=self._s2.copy(),
+                     min_x=float(bounds[0]), max_x=float(bounds[1]), min_y=float(bounds[2]), max_y=float(bounds[3]),
+                     fx=cam.fx, fy=cam.fy, cx=cam.cx, cy=cam.cy, bf=cam.bf, keys=kps[:k].copy(),
+                     depth=dep[:k].copy())
+
+    def mono_frame(self, image: np.ndarray, camera, rgb: bool = True, gray_mode: int = L.GRAY_SHIFT15):
+        """The monocular Frame (Frame.cc:216-277 behind Tracking::GrabImageMonocular's cvtColor): `image` is
+        CV_8UC1, or CV_8UC3 / CV_8UC4 with channel 0 = R when `rgb` (mbRGB) else B. `camera` is an
+        _lib.camera or a dict of fx, fy, cx, cy, dist, bf. Returns a frames.Frame with keys (mvKeys),
+        keys_un, the image bounds and grid inverses, and u_right = depth = -1."""
+        return self._sensor_frame(image, camera, None, 1.0, rgb, gray_mode)
+
+    def rgbd_frame(self, image: np.ndarray, depth_map: np.ndarray, camera, depth_factor: float = 1.0,
+                   rgb: bool = True, gray_mode: int = L.GRAY_SHIFT15):
+        """The RGB-D Frame (Frame.cc:154-214 behind Tracking::GrabImageRGBD): as mono_frame, plus
+        ComputeStereoFromRGBD on the raw uint16 / float32 `depth_map`; `depth_factor` is mDepthMapFactor
+        already inverted (Tracking.cc:148-152)."""
+        return self._sensor_frame(image, camera, depth_map, depth_factor, rgb, gray_mode)
+
+    def to_gray_batch(self, src, dst, rgb: bool = True, gray_mode: int = L.GRAY_SHIFT15,
+                      stream: Optional[int] = None) -> None:
+        """cvtColor(*2GRAY) on device tensors: src (n, rows, cols, 3 or 4) uint8, dst (n, rows, cols) uint8,
+        both with contiguous pixels (any row and image strides). Async on `stream` (default: the handle's)."""
+        if src.dim() != 4 or dst.dim() != 3 or src.shape[:3] != dst.shape or src.shape[3] not in (3, 4):
+            raise ValueError("to_gray_batch: src (n, rows, cols, 3|4), dst (n, rows, cols)")
+        if src.stride(3) != 1 or src.stride(2) != src.shape[3] or dst.stride(2) != 1:
+            raise ValueError("to_gray_batch: pixels must be contiguous within a row")
+        n, rows, cols, ch = src.shape
+        L.check(self._lib.orbfe_gray_batch_device(
+            self._h, n, c_void_p(src.data_ptr()), c_size_t(src.stride(0)), c_size_t(src.stride(1)), ch,
+            int(bool(rgb)), int(gray_mode), rows, cols, c_void_p(dst.data_ptr()), c_size_t(dst.stride(0)),
+            c_size_t(dst.stride(1)), c_void_p(stream or 0)), "orbfe_gray_batch_device")
+
+    def frame_finish_batch(self, n_images: int, camera, d_kps: int, d_counts: int, cap: int, rows: int, cols: int,
+                           d_keys_un: int, d_u_right: int, d_depth: int, depth_maps=None,
+                           depth_factor: float = 1.0, stream: Optional[int] = None) -> None:
+        """UndistortKeyPoints + ComputeStereoFromRGBD of a device batch (orbfe_frame_finish_batch_device): the
+        int arguments are device addresses laid out as extract_batch_device's outputs; depth_maps is a
+        (n, rows, cols) uint16 / float32 device tensor (any row and image strides) or None (monocular)."""
+        cam = camera if isinstance(camera, L.camera) else L.make_camera(**camera)
+        dm, ist, pitch, dtype = 0, 0, 0, L.DEPTH_F32
+        if depth_maps is not None:
+            es = depth_maps.element_size()
+            if depth_maps.dim() != 3 or depth_maps.stride(2) != 1 or es not in (2, 4) or \
+                    (es == 4 and not depth_maps.is_floating_point()):
+                raise ValueError("frame_finish_batch: depth_maps (n, rows, cols) of 16-bit raw values or float32")
+            dm, ist, pitch = depth_maps.data_ptr(), depth_maps.stride(0) * es, depth_maps.stride(1) * es
+            dtype = L.DEPTH_U16 if es == 2 else L.DEPTH_F32
+        L.check(self._lib.orbfe_frame_finish_batch_device(
+            self._h, int(n_images), byref(cam), c_void_p(d_kps), c_void_p(d_counts), int(cap), c_void_p(dm),
+            c_size_t(ist), c_size_t(pitch), dtype, float(depth_factor), int(rows), int(cols), c_void_p(d_keys_un),
+            c_void_p(d_u_right), c_void_p(d_depth), c_void_p(stream or 0)), "orbfe_frame_finish_batch_device")
+
     def compute_stereo_matches_batch_device(self, n_pairs: int, left0: int, right0: int, d_kps: int,
                                             d_desc: int, d_counts: int, cap: int, mbf: float,
                                             mb: float, d_u_right: int, d_depth: int,
@@ -377,6 +468,48 @@ class ORBextractor:
         L.check(self._lib.orbfe_debug_geometry(self._h, rows, cols, L.ptr(info), len(info)),
                 "geometry")
         return info.reshape(self.nlevels, 7)
+
+
+def image_bounds(camera, rows: int, cols: int) -> np.ndarray:
+    """Frame::ComputeImageBounds (Frame.cc:488-520): float32 (mnMinX, mnMaxX, mnMinY, mnMaxY)."""
+    cam = camera if isinstance(camera, L.camera) else L.make_camera(**camera)
+    out = np.zeros(4, np.float32)
+    L.check(L.lib().orbfe_image_bounds(byref(cam), int(rows), int(cols), L.ptr(out)), "orbfe_image_bounds")
+    return out
+
+
+def undistort_keypoints_host(camera, keys: KeyPoints) -> KeyPoints:
+    """Frame::UndistortKeyPoints (Frame.cc:456-486) on host arrays: mvKeysUn of mvKeys."""
+    cam = camera if isinstance(camera, L.camera) else L.make_camera(**camera)
+    k = np.ascontiguousarray(keys, L.KEYPOINT_DTYPE)
+    out = np.zeros(len(k), L.KEYPOINT_DTYPE)
+    L.check(L.lib().orbfe_undistort_keypoints_host(byref(cam), L.ptr(k), len(k), L.ptr(out)),
+            "orbfe_undistort_keypoints_host")
+    return out
+
+
+def stereo_from_depth_host(camera, keys: KeyPoints, keys_un: KeyPoints, depth_map: Optional[np.ndarray],
+                           depth_factor: float = 1.0):
+    """Frame::ComputeStereoFromRGBD (Frame.cc:702-723) on host arrays: (mvuRight, mvDepth). depth_map is the raw
+    uint16 / float32 map (contiguous within a row; any row stride) or None."""
+    cam = camera if isinstance(camera, L.camera) else L.make_camera(**camera)
+    k = np.ascontiguousarray(keys, L.KEYPOINT_DTYPE)
+    u = np.ascontiguousarray(keys_un, L.KEYPOINT_DTYPE)
+    ur = np.zeros(len(k), np.float32)
+    dep = np.zeros(len(k), np.float32)
+    rows = cols = pitch = address = 0
+    dtype = L.DEPTH_F32
+    if depth_map is not None:
+        if depth_map.dtype not in (np.uint16, np.float32) or depth_map.ndim != 2 or \
+                depth_map.strides[1] != depth_map.itemsize:
+            raise ValueError("the depth map is a 2-D uint16 or float32 array with contiguous rows")
+        rows, cols = depth_map.shape
+        dtype = L.DEPTH_U16 if depth_map.dtype == np.uint16 else L.DEPTH_F32
+        pitch, address = depth_map.strides[0], depth_map.ctypes.data
+    L.check(L.lib().orbfe_stereo_from_depth_host(byref(cam), L.ptr(k), L.ptr(u), len(k), c_void_p(address),
+                                                 c_size_t(pitch), dtype, float(depth_factor), rows, cols,
+                                                 L.ptr(ur), L.ptr(dep)), "orbfe_stereo_from_depth_host")
+    return ur, dep
 
 
 def register_host(a: np.ndarray) -> None:

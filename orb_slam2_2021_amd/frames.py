@@ -43,6 +43,8 @@ class Frame:
     bf: float = 0.0                # mbf
     tcw: Optional[np.ndarray] = None          # mTcw rows 0..2 (3x4 float32)
     feat_vec: Optional["FeatureVector"] = None  # mFeatVec (KeyFrame)
+    keys: Optional[np.ndarray] = None         # mvKeys (the distorted keypoints), where they differ from keys_un
+    depth: Optional[np.ndarray] = None        # mvDepth, float32 (-1 = none)
 
     def __post_init__(self):
         self.keys_un = np.ascontiguousarray(self.keys_un, dtype=L.KEYPOINT_DTYPE)
@@ -54,6 +56,10 @@ class Frame:
         self.level_sigma2 = np.ascontiguousarray(self.level_sigma2, dtype=np.float32)
         if self.tcw is not None:
             self.tcw = np.ascontiguousarray(self.tcw, dtype=np.float32).reshape(3, 4)
+        if self.keys is not None:
+            self.keys = np.ascontiguousarray(self.keys, dtype=L.KEYPOINT_DTYPE).reshape(n)
+        if self.depth is not None:
+            self.depth = np.ascontiguousarray(self.depth, dtype=np.float32).reshape(n)
 
     @property
     def N(self) -> int:
