@@ -2,7 +2,7 @@
 orbfe_vocab.h, orbfe_stereo.h, orbfe_frustum.h, orbfe_keyframe.h, orbfe_pack.h, orbfe_c3.h,
 orbfe_kfdb.h, orbfe_sim3.h, orbfe_triangulate.h, orbfe_pnp.h, orbfe_poseopt.h,
 orbfe_optsim3.h, orbfe_lba.h, orbfe_essgraph.h, orbfe_gba.h, orbfe_init.h, orbfe_covis.h, orbfe_localmap.h,
-orbfe_mapcorr.h, orbfe_frame.h).
+orbfe_mapcorr.h, orbfe_frame.h, orbfe_gridmap.h).
 
 The shared library is the product: every compute call below runs the HIP kernels in it. There is
 no CPU fallback -- if the library is missing, or no HIP device is present when a compute handle is
@@ -406,6 +406,20 @@ def make_camera(fx, fy, cx, cy, dist, bf) -> camera:
     return c
 
 
+GRIDMAP_REFERENCE, GRIDMAP_INTENDED = 0, 1  # orbfe_gridmap.h: the two rule sets
+GRIDMAP_SEGMENT, GRIDMAP_MAX_KEYFRAMES, GRIDMAP_MAX_POINTS = 64, 4096, 8192
+
+
+class gridmap_geometry(Structure):  # orbfe_gridmap.h
+    _fields_ = [("scale_factor", c_int32), ("min_x", c_float), ("max_x", c_float), ("min_z", c_float),
+                ("max_z", c_float), ("visit_threshold", c_int32)]
+
+
+class gridmap_stats(Structure):
+    _fields_ = [("beams", ctypes.c_int64), ("visits", ctypes.c_int64), ("dropped", ctypes.c_int64),
+                ("points_cut", ctypes.c_int64), ("kf_outside", c_int32), ("row0", c_int32), ("row1", c_int32)]
+
+
 # name -> (restype, argtypes)
 _SIGNATURES = {
     "orbfe_last_error": (c_char_p, []),
@@ -625,6 +639,25 @@ _SIGNATURES = {
                                                c_void_p, c_void_p]),
     "orbfe_covis_local_geometry": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p,
                                            POINTER(covis_local_geometry)]),
+    # orbfe_gridmap.h
+    "orbfe_gridmap_default_geometry": (c_int, [POINTER(gridmap_geometry)]),
+    "orbfe_gridmap_dims": (c_int, [POINTER(gridmap_geometry), POINTER(c_int32), POINTER(c_int32), POINTER(c_float),
+                                   POINTER(c_float)]),
+    "orbfe_gridmap_create": (c_int, [c_int, POINTER(gridmap_geometry), c_int, POINTER(c_void_p)]),
+    "orbfe_gridmap_destroy": (c_int, [c_void_p]),
+    "orbfe_gridmap_reset": (c_int, [c_void_p]),
+    "orbfe_gridmap_update": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(gridmap_stats)]),
+    "orbfe_gridmap_update_resident": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, POINTER(gridmap_stats),
+                                              POINTER(c_int32)]),
+    "orbfe_gridmap_build": (c_int, [c_void_p, c_int]),
+    "orbfe_gridmap_download": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "orbfe_gridmap_download_counters": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "orbfe_gridmap_upload_counters": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "orbfe_gridmap_probability": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "orbfe_gridmap_host_update": (c_int, [POINTER(gridmap_geometry), c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_void_p, POINTER(gridmap_stats)]),
+    "orbfe_gridmap_host_build": (c_int, [POINTER(gridmap_geometry), c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p]),
     # orbfe_poseopt.h
     "orbfe_poseopt_create": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
     "orbfe_poseopt_destroy": (c_int, [c_void_p]),

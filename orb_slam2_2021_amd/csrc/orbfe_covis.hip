@@ -39,6 +39,7 @@
 #include "../../include/orbfe_covis.h"
 #include "../../include/orbfe_localmap.h"
 #include "orbfe_covis_core.h"
+#include "orbfe_covis_view.h"
 #include "orbfe_cull_core.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
@@ -1785,5 +1786,28 @@ extern "C" int orbfe_covis_local_geometry(orbfe_covis* h, int n_kf, const int64_
   r->geometry.min_distance = reinterpret_cast<const float*>(g.min_d);
   r->geometry.max_distance = reinterpret_cast<const float*>(g.max_d);
   r->geometry.descriptors = reinterpret_cast<const uint8_t*>(g.desc);
+  return ORBFE_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// orbfe_covis_view.h: the rows and the geometry store as orbfe_gridmap.hip reads them. Every mutation
+// above synchronises the handle's stream before it returns, so the arrays are complete here.
+int orbfe_covis_rows_view(orbfe_covis* h, int n_kf, const int64_t* kf_ids, std::vector<int32_t>* list_rows,
+                          std::vector<int32_t>* row_len, CovisRowsView* view) {
+  if (!h || !list_rows || !row_len || !view) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_rows_view: bad argument");
+  lm::Plan plan;
+  cc::Status cs = lm::check_list(h->core, n_kf, kf_ids, list_rows, &plan);
+  if (cs) return covis_fail("orbfe_gridmap_update_resident", cs);
+  row_len->resize(n_kf);
+  for (int i = 0; i < n_kf; i++) (*row_len)[i] = std::min(std::max(h->core.row_n[(*list_rows)[i]], 0), h->core.S);
+  view->device = h->device;
+  view->rows = h->d_rows;
+  view->row_n = h->d_row_n;
+  view->bad = h->d_bad;
+  view->geo_rec = h->d_geo_rec;
+  view->geo_state = h->d_geo_state;
+  view->M = h->core.M;
+  view->S = h->core.S;
+  view->P = h->core.P;
   return ORBFE_OK;
 }
