@@ -20,12 +20,13 @@ from .map_correction import (ApplyGlobalBundleAdjustment, CorrectLoopPoses, MapC
                              gba_update_problem_of_map, loop_problem_of_map, normals_problem_of_map)
 from .matcher import ORBmatcher
 from .occupancy_grid import GridStats, OccupancyGrid
+from .rectify import StereoRectifier, rectify_entries_host, rectify_maps_host, remap_host
 from .pnp_solver import PnPBatch, PnPsolver
 from .pose_optimization import PoseOptimization, PoseOptimizer
 from .sim3_optimization import OptimizeSim3, Sim3Optimizer, problem_of_keyframes
 from .sim3_solver import Sim3Batch, Sim3Solver, solve_batch
 
-__all__ = ["OccupancyGrid", "GridStats", "ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "CovisibilityGraph", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "Initializer", "InitializerBatch", "PoseOptimizer", "PoseOptimization", "Sim3Optimizer", "OptimizeSim3", "problem_of_keyframes", "LocalBundleAdjuster", "LocalBundleAdjustment", "problem_of_local_map", "GlobalBundleAdjuster", "GlobalBundleAdjustment", "problem_of_map", "EssentialGraphOptimizer", "OptimizeEssentialGraph", "problem_of_essential_graph", "MapCorrector", "UpdateNormalAndDepth", "CorrectLoopPoses", "ApplyGlobalBundleAdjustment", "normals_problem_of_map", "loop_problem_of_map", "gba_update_problem_of_map", "Frame", "KeyFrame",
+__all__ = ["StereoRectifier", "rectify_maps_host", "remap_host", "rectify_entries_host", "OccupancyGrid", "GridStats", "ORBextractor", "ORBmatcher", "KeyFrameDatabase", "SharingList", "CovisibilityGraph", "Sim3Solver", "Sim3Batch", "solve_batch", "PnPsolver", "PnPBatch", "Initializer", "InitializerBatch", "PoseOptimizer", "PoseOptimization", "Sim3Optimizer", "OptimizeSim3", "problem_of_keyframes", "LocalBundleAdjuster", "LocalBundleAdjustment", "problem_of_local_map", "GlobalBundleAdjuster", "GlobalBundleAdjustment", "problem_of_map", "EssentialGraphOptimizer", "OptimizeEssentialGraph", "problem_of_essential_graph", "MapCorrector", "UpdateNormalAndDepth", "CorrectLoopPoses", "ApplyGlobalBundleAdjustment", "normals_problem_of_map", "loop_problem_of_map", "gba_update_problem_of_map", "Frame", "KeyFrame",
            "TriKeyFrame", "DeviceTriKeyFrame",
            "FeatureVector", "LocalMapPoints", "LastFrameMapPoints", "MapPointGeometry", "ResidentLocalMap", "KeyFrameMapPoints", "KEYPOINT_DTYPE",
            "synth_frame", "synth_sequence_frame", "register_host", "unregister_host", "OrbfeError", "LibraryMissing"]

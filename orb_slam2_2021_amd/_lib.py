@@ -388,6 +388,8 @@ TRI_MAX_KEYS, TRI_MAX_KF2_KEYS, TRI_MAX_PAIRS, TRI_MAX_NEIGHBOURS = 8192, 16384,
 
 GRAY_SHIFT15, GRAY_SHIFT14 = 0, 1  # orbfe_frame.h: cvtColor's 4.x / 2.4-3.x tables
 DEPTH_U16, DEPTH_F32 = 0, 1
+# orbfe_rectify.h: one destination pixel of a rectification plan
+RECTIFY_ENTRY_DTYPE = np.dtype([("ix", "<i2"), ("iy", "<i2"), ("alpha", "<u2"), ("outside", "<u2")])
 
 
 class camera(Structure):  # orbfe_frame.h
@@ -545,6 +547,22 @@ _SIGNATURES = {
     "orbfe_rgbd_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_size_t, c_int, c_int, c_int, c_void_p,
                                  c_size_t, c_int, c_float, POINTER(camera), c_void_p, c_void_p, POINTER(c_int),
                                  c_int, c_void_p, c_void_p, c_void_p]),
+    "orbfe_rectify_maps_host": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                        c_void_p]),
+    "orbfe_remap_host": (c_int, [c_void_p, c_int, c_int, c_size_t, c_int, c_void_p, c_void_p, c_size_t, c_int, c_int,
+                                 c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t]),
+    "orbfe_rectify_entries_host": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "orbfe_rectify_plan_create": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_int, POINTER(c_void_p)]),
+    "orbfe_rectify_plan_destroy": (None, [c_void_p]),
+    "orbfe_rectify_plan_read": (c_int, [c_void_p, c_int, c_void_p]),
+    "orbfe_rectify_batch_device": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_size_t, c_int,
+                                           c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_size_t,
+                                           c_void_p]),
+    "orbfe_rectified_stereo_frame": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_size_t, c_int,
+                                             c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p,
+                                             POINTER(c_int), c_void_p, c_void_p, POINTER(c_int), c_int, c_void_p,
+                                             c_void_p]),
     "orbfe_is_in_frustum": (c_int, [c_void_p, POINTER(frame_view), POINTER(mappoint_geometry),
                                     c_void_p, c_float, c_float, POINTER(frustum_out),
                                     POINTER(c_int)]),

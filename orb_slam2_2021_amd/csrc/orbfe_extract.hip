@@ -2553,6 +2553,8 @@ struct orbfe_extractor {
   OrbfeStereoScratch* stereo = nullptr;
   // the monocular / RGB-D Frames' staging buffers (orbfe_frame.hip)
   OrbfeFrameScratch* frame = nullptr;
+  // the raw-pair stereo Frame's staging buffers (orbfe_rectify.hip)
+  OrbfeRectifyScratch* rectify = nullptr;
   // launch_extract's enqueue sequence captured once per distinct set of arguments and replayed as
   // a hipGraph (orbfe_extractor_set_graphs; `graphs` keyed by everything the sequence depends on).
   // Off by default: measured slower on MI355X / ROCm 7.2
@@ -3479,6 +3481,7 @@ extern "C" int orbfe_extractor_destroy(orbfe_extractor* h) {
   if (h->d2h) hipStreamSynchronize(h->d2h);  // (the host-pyramid prefetch reads d_pyr)
   orbfe_internal_stereo_free(h->stereo);
   orbfe_internal_frame_free(h->frame);
+  orbfe_internal_rectify_free(h->rectify);
   drop_graphs(h);
   free_batch(h);
   hipFree(h->d_levels);
@@ -4061,6 +4064,7 @@ int orbfe_internal_pyramid(orbfe_extractor* h, OrbfePyramid* out) {
 
 OrbfeStereoScratch** orbfe_internal_stereo_slot(orbfe_extractor* h) { return &h->stereo; }
 OrbfeFrameScratch** orbfe_internal_frame_slot(orbfe_extractor* h) { return &h->frame; }
+OrbfeRectifyScratch** orbfe_internal_rectify_slot(orbfe_extractor* h) { return &h->rectify; }
 int orbfe_internal_device(orbfe_extractor* h, hipStream_t* stream) {
   *stream = h->stream;
   return h->device;

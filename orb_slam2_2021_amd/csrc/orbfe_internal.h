@@ -52,3 +52,9 @@ int orbfe_internal_device(orbfe_extractor* h, hipStream_t* stream);
 struct OrbfeFrameScratch;
 OrbfeFrameScratch** orbfe_internal_frame_slot(orbfe_extractor* h);
 void orbfe_internal_frame_free(OrbfeFrameScratch* s);
+
+// Staging buffers of the raw-pair stereo Frame owned by the handle (created lazily by orbfe_rectify.hip,
+// freed with the handle).
+struct OrbfeRectifyScratch;
+OrbfeRectifyScratch** orbfe_internal_rectify_slot(orbfe_extractor* h);
+void orbfe_internal_rectify_free(OrbfeRectifyScratch* s);

@@ -207,6 +207,44 @@ class ORBextractor:
         return (kl[:a].copy(), dl[:a].copy() if a else None, kr[:b].copy(),
                 dr[:b].copy() if b else None, ur[:a].copy(), dep[:a].copy())
 
+    def rectified_stereo_frame(self, left: np.ndarray, right: np.ndarray, rectifier, mbf: float, mb: float,
+                               rgb: bool = True, gray_mode: int = L.GRAY_SHIFT15,
+                               rows: Tuple[int, Optional[int]] = (0, None)):
+        """The stereo Frame from a raw, distorted pair (arducam_images.cpp:119-153, Tracking.cc:183-208,
+        Frame.cc:113-125): remap with `rectifier` (a rectify.StereoRectifier), crop to rectified rows
+        [rows[0], rows[1]), gray, ExtractORB of both planes, ComputeStereoMatches. left / right: CV_8UC1,
+        CV_8UC3 or CV_8UC4 of the rectifier's source size; the two halves of one side-by-side array go up in
+        one copy. Returns what stereo_frame returns."""
+        l, r = np.asarray(left), np.asarray(right)
+        if l.dtype != np.uint8 or r.dtype != np.uint8 or l.shape != r.shape or l.ndim not in (2, 3) or \
+                (l.ndim == 3 and l.shape[2] not in (1, 3, 4)):
+            raise ValueError("rectified_stereo_frame needs two same-shaped CV_8UC1, CV_8UC3 or CV_8UC4 images")
+        channels = 1 if l.ndim == 2 else l.shape[2]
+        dense = (channels, 1) if l.ndim == 3 else (1,)
+        if l.size and (l.strides[1:] != dense or r.strides != l.strides or l.strides[0] < l.shape[1] * channels):
+            l, r = np.ascontiguousarray(l), np.ascontiguousarray(r)
+        row0, row1 = int(rows[0]), rectifier.rows if rows[1] is None else int(rows[1])
+        e = np.zeros(0, L.KEYPOINT_DTYPE)
+        if l.size == 0 or row1 == row0:
+            return e, None, e.copy(), None, np.zeros(0, np.float32), np.zeros(0, np.float32)
+        cap = self.max_keypoints(max(row1 - row0, 1), rectifier.cols)
+        kl = np.zeros(cap, L.KEYPOINT_DTYPE)
+        kr = np.zeros(cap, L.KEYPOINT_DTYPE)
+        dl = np.zeros((cap, 32), np.uint8)
+        dr = np.zeros((cap, 32), np.uint8)
+        ur = np.zeros(cap, np.float32)
+        dep = np.zeros(cap, np.float32)
+        nl, nr = c_int(), c_int()
+        L.check(self._lib.orbfe_rectified_stereo_frame(
+            self._h, rectifier._plan, c_void_p(l.ctypes.data), c_void_p(r.ctypes.data), l.shape[0], l.shape[1],
+            c_size_t(l.strides[0]), channels, int(bool(rgb)), int(gray_mode), row0, row1, float(mbf), float(mb),
+            L.ptr(kl), L.ptr(dl), byref(nl), L.ptr(kr), L.ptr(dr), byref(nr), cap, L.ptr(ur), L.ptr(dep)),
+            "orbfe_rectified_stereo_frame")
+        self._last_shape = (row1 - row0, rectifier.cols)
+        a, b = nl.value, nr.value
+        return (kl[:a].copy(), dl[:a].copy() if a else None, kr[:b].copy(),
+                dr[:b].copy() if b else None, ur[:a].copy(), dep[:a].copy())
+
     # ---- the monocular and RGB-D Frames (src/Frame.cc:154-277; include/orbfe_frame.h) --------
     def _sensor_frame(self, image, camera, depth_map, depth_factor, rgb, gray_mode):
         from .frames import Frame
