@@ -22,6 +22,7 @@
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
 #include "orbfe_lba_core.h"
+#include "orbfe_stage.h"
 
 #define BA_BLOCK 128
 
@@ -89,20 +90,9 @@ static __global__ __launch_bounds__(LBA_LANES) void k_ba_reduce(LbaWs w, int mod
 // ------------------------------------------------------------------------------------------
 // host
 
-// A handle's device pool, carved in 256-byte steps; with base == nullptr only the size is computed
-struct BaPool {
-  uint8_t* base;
-  size_t off = 0;
-  template <class T>
-  void take(T*& field, size_t count) {
-    field = reinterpret_cast<T*>(base ? base + off : nullptr);
-    off += (sizeof(T) * count + 255) & ~(size_t)255;
-  }
-};
-
-// The LbaWs part of the pool. nf: the bound on the free keyframes, which is the bound on the slots;
+// The LbaWs part of a handle's device pool (a counting block only sizes it). nf: the bound on the free keyframes, which is the bound on the slots;
 // dense: the local adjuster's S, Lm, Mm (the global one's reduced system is its envelope)
-inline void ba_carve(BaPool& pool, LbaWs& w, size_t nk, size_t nf, size_t np, size_t ne, bool dense) {
+inline void ba_carve(OrbfeStage& pool, LbaWs& w, size_t nk, size_t nf, size_t np, size_t ne, bool dense) {
   const size_t n = 6 * nf;
   pool.take(w.cam, 5 * nk);
   pool.take(w.kf_free, nk);

@@ -44,6 +44,7 @@
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
 #include "orbfe_localmap_core.h"
+#include "orbfe_stage.h"
 
 namespace cc = orbfe_covis_core;
 namespace lm = orbfe_localmap_core;
@@ -606,10 +607,8 @@ __global__ __launch_bounds__(COVIS_ROW_THREADS) void k_covis_cull_points(CovisCu
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_covis {
-  int device = -1;
+struct orbfe_covis : OrbfeDev {
   cc::Core core;
-  hipStream_t stream = nullptr;
   int32_t* d_rows = nullptr;
   int32_t* d_row_n = nullptr;
   uint8_t* d_bad = nullptr;
@@ -644,8 +643,6 @@ struct orbfe_covis {
   int geo_out_cap = 0;
 };
 
-static size_t covis_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static int covis_fail(const char* fn, const cc::Status& st) {
   return orbfe_set_error(st.code, (std::string(fn) + ": " + st.msg).c_str());
 }
@@ -660,7 +657,7 @@ static int covis_stage_reserve(orbfe_covis* h, size_t bytes) {
   h->h_stage = nullptr;
   h->d_stage = nullptr;
   h->stage_cap = 0;
-  const size_t cap = covis_al(bytes + bytes / 2);
+  const size_t cap = orbfe_al256(bytes + bytes / 2);
   ORBFE_HIP_CHECK(hipHostMalloc((void**)&h->h_stage, cap, hipHostMallocDefault));
   ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_stage, cap));
   h->stage_cap = cap;
@@ -669,7 +666,7 @@ static int covis_stage_reserve(orbfe_covis* h, size_t bytes) {
 
 static size_t covis_stage_take(orbfe_covis* h, size_t bytes) {
   const size_t off = h->stage_used;
-  h->stage_used += covis_al(bytes);
+  h->stage_used += orbfe_al256(bytes);
   return off;
 }
 
@@ -695,7 +692,7 @@ static int covis_res_reserve(orbfe_covis* h, size_t bytes) {
   h->h_res = nullptr;
   h->d_res = nullptr;
   h->res_cap = 0;
-  const size_t cap = covis_al(bytes + bytes / 2);
+  const size_t cap = orbfe_al256(bytes + bytes / 2);
   ORBFE_HIP_CHECK(hipHostMalloc((void**)&h->h_res, cap, hipHostMallocDefault));
   ORBFE_HIP_CHECK(hipMalloc((void**)&h->d_res, cap));
   h->res_cap = cap;
@@ -714,57 +711,41 @@ extern "C" int orbfe_covis_create(int device, int max_keyframes, int max_slots, 
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_covis_create: no such HIP device");
-  }
-  h->device = device;
-  const size_t M = (size_t)max_keyframes, S = (size_t)max_slots, P = (size_t)max_point_id;
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int open_st = orbfe_dev_open(h, device, "orbfe_covis_create");
+  if (open_st != ORBFE_OK) {
     orbfe_covis_destroy(h);
-    return st;
-  };
-#define COVIS_TRY(expr)                             \
-  do {                                              \
-    hipError_t _e = (expr);                         \
-    if (_e != hipSuccess) return fail(_e, #expr);   \
-  } while (0)
-  COVIS_TRY(hipSetDevice(device));
-  COVIS_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  COVIS_TRY(hipMalloc((void**)&h->d_rows, 4 * M * S));
-  COVIS_TRY(hipMalloc((void**)&h->d_row_n, 4 * M));
-  COVIS_TRY(hipMalloc((void**)&h->d_bad, P));
-  COVIS_TRY(hipMalloc((void**)&h->d_a, 4 * (P + 1)));
-  COVIS_TRY(hipMalloc((void**)&h->d_b, 4 * (P + 1)));
-  COVIS_TRY(hipMalloc((void**)&h->d_c, 4 * (P + 1)));
-  COVIS_TRY(hipMalloc((void**)&h->d_tops, 4 * 4096));
-  COVIS_TRY(hipMalloc((void**)&h->d_id_rank_of_row, 4 * M));
-  COVIS_TRY(hipMalloc((void**)&h->d_tie_of_idrank, 2 * M));
-  COVIS_TRY(hipMalloc((void**)&h->d_is_local, M));
-  COVIS_TRY(hipMalloc((void**)&h->d_seen, 4 * M));
-  COVIS_TRY(hipMalloc((void**)&h->d_order, 4 * M));
-  COVIS_TRY(hipMalloc((void**)&h->d_attr, M * S));
-  COVIS_TRY(hipMalloc((void**)&h->d_row_at_idrank, 4 * M));
-  COVIS_TRY(hipMalloc((void**)&h->d_culled, 4 * M));
-  COVIS_TRY(hipMemsetAsync(h->d_row_at_idrank, 0, 4 * M, h->stream));
-  COVIS_TRY(hipMemsetAsync(h->d_row_n, 0xff, 4 * M, h->stream));
-  COVIS_TRY(hipMemsetAsync(h->d_bad, 0, P, h->stream));
-  COVIS_TRY(hipMemsetAsync(h->d_a, 0, 4 * (P + 1), h->stream));
-  COVIS_TRY(hipMemsetAsync(h->d_id_rank_of_row, 0, 4 * M, h->stream));
-  COVIS_TRY(hipMemsetAsync(h->d_tie_of_idrank, 0, 2 * M, h->stream));
-  COVIS_TRY(hipStreamSynchronize(h->stream));
-#undef COVIS_TRY
+    return open_st;
+  }
+  const size_t M = (size_t)max_keyframes, S = (size_t)max_slots, P = (size_t)max_point_id;
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_rows, 4 * M * S));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_row_n, 4 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_bad, P));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_a, 4 * (P + 1)));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_b, 4 * (P + 1)));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_c, 4 * (P + 1)));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_tops, 4 * 4096));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_id_rank_of_row, 4 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_tie_of_idrank, 2 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_is_local, M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_seen, 4 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_order, 4 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_attr, M * S));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_row_at_idrank, 4 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMalloc((void**)&h->d_culled, 4 * M));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMemsetAsync(h->d_row_at_idrank, 0, 4 * M, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMemsetAsync(h->d_row_n, 0xff, 4 * M, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMemsetAsync(h->d_bad, 0, P, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMemsetAsync(h->d_a, 0, 4 * (P + 1), h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMemsetAsync(h->d_id_rank_of_row, 0, 4 * M, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipMemsetAsync(h->d_tie_of_idrank, 0, 2 * M, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_covis_destroy, hipStreamSynchronize(h->stream));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_covis_destroy(orbfe_covis* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+  if (orbfe_dev_close(h)) {
     hipFree(h->d_rows);
     hipFree(h->d_row_n);
     hipFree(h->d_bad);
@@ -790,7 +771,6 @@ extern "C" int orbfe_covis_destroy(orbfe_covis* h) {
     hipFree(h->d_geo_out);
     if (h->h_stage) hipHostFree(h->h_stage);
     if (h->h_res) hipHostFree(h->h_res);
-    if (h->stream) hipStreamDestroy(h->stream);
   }
   delete h;
   return ORBFE_OK;
@@ -804,7 +784,7 @@ extern "C" int orbfe_covis_set_keyframe(orbfe_covis* h, int64_t kf_id, uint64_t 
   if (cs) return covis_fail("orbfe_covis_set_keyframe", cs);
   if (h->device >= 0) {
     hipSetDevice(h->device);
-    int st = covis_stage_reserve(h, covis_al(4 * (size_t)n_slots) + 256);
+    int st = covis_stage_reserve(h, orbfe_al256(4 * (size_t)n_slots) + 256);
     if (st) return st;
     st = covis_upload(h, point_ids, 4 * (size_t)n_slots, h->d_rows + (size_t)row * h->core.S, nullptr);
     if (st) return st;
@@ -826,7 +806,7 @@ extern "C" int orbfe_covis_set_slots(orbfe_covis* h, int64_t kf_id, int n, const
   const int m = (int)h->tmp_slots.size();
   if (h->device >= 0 && m > 0) {
     hipSetDevice(h->device);
-    int st = covis_stage_reserve(h, 2 * covis_al(4 * (size_t)m));
+    int st = covis_stage_reserve(h, 2 * orbfe_al256(4 * (size_t)m));
     if (st) return st;
     const void *d_slots, *d_ids;
     st = covis_upload(h, h->tmp_slots.data(), 4 * (size_t)m, nullptr, &d_slots);
@@ -866,7 +846,7 @@ extern "C" int orbfe_covis_set_points_bad(orbfe_covis* h, int n, const int32_t* 
     if (point_ids[i] < 0) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_covis_set_points_bad: a point id below 0");
   if (h->device >= 0 && n > 0) {
     hipSetDevice(h->device);
-    int st = covis_stage_reserve(h, covis_al(4 * (size_t)n));
+    int st = covis_stage_reserve(h, orbfe_al256(4 * (size_t)n));
     if (st) return st;
     const void* d_ids;
     st = covis_upload(h, point_ids, 4 * (size_t)n, nullptr, &d_ids);
@@ -924,7 +904,7 @@ static CovisTable covis_table(const orbfe_covis* h) {
 }
 
 static size_t covis_refresh_bytes(const orbfe_covis* h) {
-  return 2 * covis_al(4 * (size_t)h->core.M) + covis_al(2 * (size_t)h->core.M);
+  return 2 * orbfe_al256(4 * (size_t)h->core.M) + orbfe_al256(2 * (size_t)h->core.M);
 }
 
 static int covis_max_row(const orbfe_covis* h) {
@@ -1016,7 +996,7 @@ extern "C" int orbfe_covis_update_connections(orbfe_covis* h, int n, const int64
   if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "covisibility table is host-only (device < 0)");
   if (n == 0) return ORBFE_OK;
   hipSetDevice(h->device);
-  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + 2 * covis_al(4 * (size_t)n));
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + 2 * orbfe_al256(4 * (size_t)n));
   if (st) return st;
   st = covis_refresh(h);
   if (st) return st;
@@ -1075,8 +1055,8 @@ extern "C" int orbfe_covis_vote(orbfe_covis* h, int n_queries, const int32_t* be
   if (n_queries == 0) return ORBFE_OK;
   hipSetDevice(h->device);
   const int total = begin[n_queries];
-  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + covis_al(4 * ((size_t)n_queries + 1)) +
-                                      covis_al(4 * (size_t)total));
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + orbfe_al256(4 * ((size_t)n_queries + 1)) +
+                                      orbfe_al256(4 * (size_t)total));
   if (st) return st;
   st = covis_refresh(h);
   if (st) return st;
@@ -1128,7 +1108,7 @@ extern "C" int orbfe_covis_local_map(orbfe_covis* h, int n_local, const int64_t*
   if (n_local == 0) return ORBFE_OK;
   hipSetDevice(h->device);
   cc::Core& c = h->core;
-  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + covis_al(4 * (size_t)n_local) + covis_al((size_t)c.M));
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + orbfe_al256(4 * (size_t)n_local) + orbfe_al256((size_t)c.M));
   if (st) return st;
   st = covis_refresh(h);
   if (st) return st;
@@ -1228,7 +1208,7 @@ extern "C" int orbfe_covis_set_keyframe_attrs(orbfe_covis* h, int64_t kf_id, int
   if (cs) return covis_fail("orbfe_covis_set_keyframe_attrs", cs);
   if (h->device >= 0 && n_slots > 0) {
     hipSetDevice(h->device);
-    int st = covis_stage_reserve(h, covis_al((size_t)n_slots));
+    int st = covis_stage_reserve(h, orbfe_al256((size_t)n_slots));
     if (st) return st;
     st = covis_upload(h, attrs, (size_t)n_slots, h->d_attr + (size_t)row * h->core.S, nullptr);
     if (st) return st;
@@ -1261,7 +1241,7 @@ extern "C" int orbfe_covis_cull_keyframes(orbfe_covis* h, int n, const int64_t* 
   if (n == 0) return ORBFE_OK;
   hipSetDevice(h->device);
   cc::Core& c = h->core;
-  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + covis_al(4 * (size_t)n) + covis_al((size_t)n));
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + orbfe_al256(4 * (size_t)n) + orbfe_al256((size_t)n));
   if (st) return st;
   st = covis_refresh(h);
   if (st) return st;
@@ -1365,7 +1345,7 @@ extern "C" int orbfe_covis_cull_points(orbfe_covis* h, int n, const int32_t* poi
   if (n == 0) return ORBFE_OK;
   hipSetDevice(h->device);
   cc::Core& c = h->core;
-  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + 3 * covis_al(4 * (size_t)n) + covis_al(8 * (size_t)n));
+  int st = covis_stage_reserve(h, covis_refresh_bytes(h) + 3 * orbfe_al256(4 * (size_t)n) + orbfe_al256(8 * (size_t)n));
   if (st) return st;
   st = covis_refresh(h);
   if (st) return st;
@@ -1594,7 +1574,7 @@ static int covis_lm_run(orbfe_covis* h, const lm::Plan& plan, int n_kf, int n_se
     h->lm_dirty = false;
   }
   if (plan.max_row == 0 || plan.bound == 0) return ORBFE_OK;  // every named row is empty
-  int st = covis_stage_reserve(h, covis_al(4 * (size_t)n_kf) + covis_al(4 * (size_t)n_seen));
+  int st = covis_stage_reserve(h, orbfe_al256(4 * (size_t)n_kf) + orbfe_al256(4 * (size_t)n_seen));
   if (st) return st;
   const size_t o_blk = 4, o_out = o_blk + (size_t)plan.n_blocks + 1, words = o_out + (size_t)plan.bound;
   st = covis_res_reserve(h, 4 * words);
@@ -1723,7 +1703,7 @@ extern "C" int orbfe_covis_set_point_geometry(orbfe_covis* h, int n, const int32
   }
   for (int b = 0; b < n; b += lm::kSetChunk) {
     const int m = std::min(lm::kSetChunk, n - b);
-    int st = covis_stage_reserve(h, covis_al(lm::kRecord * (size_t)m) + covis_al(4 * (size_t)m) + covis_al((size_t)m));
+    int st = covis_stage_reserve(h, orbfe_al256(lm::kRecord * (size_t)m) + orbfe_al256(4 * (size_t)m) + orbfe_al256((size_t)m));
     if (st) return st;
     const size_t off = covis_stage_take(h, lm::kRecord * (size_t)m);
     for (int i = 0; i < m; i++)

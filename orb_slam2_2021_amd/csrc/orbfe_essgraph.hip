@@ -31,6 +31,7 @@
 #include "orbfe_device.h"
 #include "orbfe_essgraph_core.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_stage.h"
 
 static_assert(LM_FLAG_LARGE_STEP == ORBFE_ESSGRAPH_FLAG_LARGE_STEP && LM_FLAG_NONFINITE == ORBFE_ESSGRAPH_FLAG_NONFINITE,
               "flag values");
@@ -163,69 +164,59 @@ __global__ __launch_bounds__(EG_BLOCK) void k_eg_finish(EgWs w) {
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_essgraph {
-  int device = -1;
+struct orbfe_essgraph : OrbfeDev {
   int max_v = 0, max_e = 0, max_blk = 0, max_p = 0;
-  hipStream_t stream = nullptr;
   uint8_t* d_pool = nullptr;
   size_t pool_bytes = 0;
   LmRec* h_rec = nullptr;  // pinned
   EgWs w;                  // device pointers, sized for the handle's bounds
 };
 
-static size_t eg_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // carves the device pool; with base == nullptr only the size is computed
 static size_t eg_carve(orbfe_essgraph* h, uint8_t* base) {
-  size_t off = 0;
+  OrbfeStage pool;
+  pool.d = base;
   const size_t nv = h->max_v, ne = h->max_e, nb = h->max_blk, np = h->max_p;
   EgWs& w = h->w;
-  auto take = [&](size_t bytes) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += eg_al(bytes);
-    return p;
-  };
-#define EG_TAKE(field, type, count) w.field = reinterpret_cast<type*>(take(sizeof(type) * (count)))
-  EG_TAKE(tcw, const float, 12 * nv);
-  EG_TAKE(corr_of_v, const int, nv);
-  EG_TAKE(nonc_of_v, const int, nv);
-  EG_TAKE(corr, const double, 8 * nv);
-  EG_TAKE(nonc, const double, 8 * nv);
-  EG_TAKE(e_i, const int, ne);
-  EG_TAKE(e_j, const int, ne);
-  EG_TAKE(e_kind, const uint8_t, ne);
-  EG_TAKE(xw, const float, 3 * np);
-  EG_TAKE(p_ref, const int, np);
-  EG_TAKE(slot_of_v, const int, nv);
-  EG_TAKE(v_of_slot, const int, nv);
-  EG_TAKE(ve_begin, const int, nv + 1);
-  EG_TAKE(ve_edge, const int, 2 * ne);
-  EG_TAKE(row_first, const int, nv);
-  EG_TAKE(row_off, const int, nv + 1);
-  EG_TAKE(ob_begin, const int, ne + 1);
-  EG_TAKE(ob_pos, const int, ne);
-  EG_TAKE(ob_edge, const int, ne);
-  EG_TAKE(col_begin, const int, nv + 1);
-  EG_TAKE(col_row, const int, nb);
-  EG_TAKE(scw, double, 8 * nv);
-  EG_TAKE(mst, double, 8 * nv);
-  EG_TAKE(est, double, 8 * nv);
-  EG_TAKE(tri, double, 8 * nv);
-  EG_TAKE(meas, double, 8 * ne);
-  EG_TAKE(e_state, double, EG_STATES * 7 * ne);
-  EG_TAKE(e_chi, double, ne);
-  EG_TAKE(e_prod, double, EG_EDGE_DOUBLES * ne);
-  EG_TAKE(H, double, 49 * nb);
-  EG_TAKE(L, double, 49 * nb);
-  EG_TAKE(b, double, 7 * nv);
-  EG_TAKE(d, double, 7 * nv);
-  EG_TAKE(y, double, 7 * nv);
-  EG_TAKE(x, double, 7 * nv);
-  EG_TAKE(out_tcw, float, 12 * nv);
-  EG_TAKE(out_xw, float, 3 * np);
-  EG_TAKE(rec, LmRec, 1);
-#undef EG_TAKE
-  return off;
+  pool.take(w.tcw, 12 * nv);
+  pool.take(w.corr_of_v, nv);
+  pool.take(w.nonc_of_v, nv);
+  pool.take(w.corr, 8 * nv);
+  pool.take(w.nonc, 8 * nv);
+  pool.take(w.e_i, ne);
+  pool.take(w.e_j, ne);
+  pool.take(w.e_kind, ne);
+  pool.take(w.xw, 3 * np);
+  pool.take(w.p_ref, np);
+  pool.take(w.slot_of_v, nv);
+  pool.take(w.v_of_slot, nv);
+  pool.take(w.ve_begin, nv + 1);
+  pool.take(w.ve_edge, 2 * ne);
+  pool.take(w.row_first, nv);
+  pool.take(w.row_off, nv + 1);
+  pool.take(w.ob_begin, ne + 1);
+  pool.take(w.ob_pos, ne);
+  pool.take(w.ob_edge, ne);
+  pool.take(w.col_begin, nv + 1);
+  pool.take(w.col_row, nb);
+  pool.take(w.scw, 8 * nv);
+  pool.take(w.mst, 8 * nv);
+  pool.take(w.est, 8 * nv);
+  pool.take(w.tri, 8 * nv);
+  pool.take(w.meas, 8 * ne);
+  pool.take(w.e_state, EG_STATES * 7 * ne);
+  pool.take(w.e_chi, ne);
+  pool.take(w.e_prod, EG_EDGE_DOUBLES * ne);
+  pool.take(w.H, 49 * nb);
+  pool.take(w.L, 49 * nb);
+  pool.take(w.b, 7 * nv);
+  pool.take(w.d, 7 * nv);
+  pool.take(w.y, 7 * nv);
+  pool.take(w.x, 7 * nv);
+  pool.take(w.out_tcw, 12 * nv);
+  pool.take(w.out_xw, 3 * np);
+  pool.take(w.rec, 1);
+  return pool.off;
 }
 
 extern "C" int orbfe_essgraph_create(int device, int max_vertices, int max_edges, int max_env_blocks, int max_points,
@@ -245,28 +236,14 @@ extern "C" int orbfe_essgraph_create(int device, int max_vertices, int max_edges
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_essgraph_create: no such HIP device");
-  }
-  h->device = device;
-  h->pool_bytes = eg_carve(h, nullptr);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int open_st = orbfe_dev_open(h, device, "orbfe_essgraph_create");
+  if (open_st != ORBFE_OK) {
     orbfe_essgraph_destroy(h);
-    return st;
-  };
-#define EG_TRY(expr)                              \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  EG_TRY(hipSetDevice(device));
-  EG_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  EG_TRY(hipMalloc(&h->d_pool, h->pool_bytes));
-  EG_TRY(hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
-#undef EG_TRY
+    return open_st;
+  }
+  h->pool_bytes = eg_carve(h, nullptr);
+  ORBFE_CREATE_HIP(h, orbfe_essgraph_destroy, hipMalloc(&h->d_pool, h->pool_bytes));
+  ORBFE_CREATE_HIP(h, orbfe_essgraph_destroy, hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
   eg_carve(h, h->d_pool);
   *out = h;
   return ORBFE_OK;
@@ -274,12 +251,9 @@ extern "C" int orbfe_essgraph_create(int device, int max_vertices, int max_edges
 
 extern "C" int orbfe_essgraph_destroy(orbfe_essgraph* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+  if (orbfe_dev_close(h)) {
     hipFree(h->d_pool);
     if (h->h_rec) hipHostFree(h->h_rec);
-    if (h->stream) hipStreamDestroy(h->stream);
   }
   delete h;
   return ORBFE_OK;

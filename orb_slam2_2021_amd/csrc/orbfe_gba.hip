@@ -99,10 +99,8 @@ __global__ __launch_bounds__(GBA_FACTOR_THREADS) void k_gba_subst(GbaWs g) {
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_gba {
-  int device = -1;
+struct orbfe_gba : OrbfeDev {
   int max_kf = 0, max_points = 0, max_edges = 0, max_env = 0;
-  hipStream_t stream = nullptr;
   uint8_t* d_pool = nullptr;
   size_t pool_bytes = 0;
   LmRec* h_rec = nullptr;  // pinned
@@ -112,7 +110,8 @@ struct orbfe_gba {
 // carves the device pool; with base == nullptr only the size is computed
 static size_t gba_carve(orbfe_gba* h, uint8_t* base) {
   const size_t nk = h->max_kf, nb = h->max_env;
-  BaPool pool = {base};
+  OrbfeStage pool;
+  pool.d = base;
   ba_carve(pool, h->g.l, nk, nk, h->max_points, h->max_edges, false);
   EnvWs& e = h->g.env;
   pool.take(e.row_first, nk);
@@ -141,28 +140,14 @@ extern "C" int orbfe_gba_create(int device, int max_kf, int max_points, int max_
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_gba_create: no such HIP device");
-  }
-  h->device = device;
-  h->pool_bytes = gba_carve(h, nullptr);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int open_st = orbfe_dev_open(h, device, "orbfe_gba_create");
+  if (open_st != ORBFE_OK) {
     orbfe_gba_destroy(h);
-    return st;
-  };
-#define GBA_TRY(expr)                             \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  GBA_TRY(hipSetDevice(device));
-  GBA_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  GBA_TRY(hipMalloc(&h->d_pool, h->pool_bytes));
-  GBA_TRY(hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
-#undef GBA_TRY
+    return open_st;
+  }
+  h->pool_bytes = gba_carve(h, nullptr);
+  ORBFE_CREATE_HIP(h, orbfe_gba_destroy, hipMalloc(&h->d_pool, h->pool_bytes));
+  ORBFE_CREATE_HIP(h, orbfe_gba_destroy, hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
   gba_carve(h, h->d_pool);
   *out = h;
   return ORBFE_OK;
@@ -170,12 +155,9 @@ extern "C" int orbfe_gba_create(int device, int max_kf, int max_points, int max_
 
 extern "C" int orbfe_gba_destroy(orbfe_gba* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+  if (orbfe_dev_close(h)) {
     hipFree(h->d_pool);
     if (h->h_rec) hipHostFree(h->h_rec);
-    if (h->stream) hipStreamDestroy(h->stream);
   }
   delete h;
   return ORBFE_OK;

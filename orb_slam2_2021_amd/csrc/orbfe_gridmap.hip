@@ -39,6 +39,7 @@
 #include "orbfe_gridmap_core.h"
 #include "orbfe_ktimer.h"
 #include "orbfe_localmap_core.h"
+#include "orbfe_stage.h"
 
 namespace lm = orbfe_localmap_core;
 
@@ -390,15 +391,13 @@ __global__ __launch_bounds__(GM_THREADS) void k_gm_probability(const int32_t* oc
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_gridmap {
-  int device = -1;
+struct orbfe_gridmap : OrbfeDev {
   int rules = ORBFE_GRIDMAP_REFERENCE;
   GmGrid g{};
   long long cells = 0, cells_pad = 0;
   int spb = 1;      // segments of the longest beam
   int seg_cap = 0;  // entries of the segment arrays
   int sub = 0;      // beams per sub-range
-  hipStream_t stream = nullptr;
   int32_t* d_occupied = nullptr;
   int32_t* d_visits = nullptr;
   int8_t* d_grid = nullptr;
@@ -440,54 +439,38 @@ extern "C" int orbfe_gridmap_create(int device, const orbfe_gridmap_geometry* ge
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_gridmap_create: no such HIP device");
-  }
-  h->device = device;
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int open_st = orbfe_dev_open(h, device, "orbfe_gridmap_create");
+  if (open_st != ORBFE_OK) {
     orbfe_gridmap_destroy(h);
-    return st;
-  };
-#define GM_TRY(expr)                              \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
+    return open_st;
+  }
   const size_t pad = (size_t)h->cells_pad, cap = (size_t)h->seg_cap;
-  GM_TRY(hipSetDevice(device));
-  GM_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  GM_TRY(hipMalloc((void**)&h->d_occupied, 4 * pad));
-  GM_TRY(hipMalloc((void**)&h->d_visits, 4 * pad));
-  GM_TRY(hipMalloc((void**)&h->d_grid, pad));
-  GM_TRY(hipMalloc((void**)&h->d_pos, 12 * (size_t)GM_GROUP));
-  GM_TRY(hipMalloc((void**)&h->d_rec, 16 * (size_t)GM_GROUP));
-  GM_TRY(hipMalloc((void**)&h->d_seg, 4 * (size_t)GM_GROUP));
-  GM_TRY(hipMalloc((void**)&h->d_seg_xy, 8 * cap));
-  GM_TRY(hipMalloc((void**)&h->d_seg_err, 8 * cap));
-  GM_TRY(hipMalloc((void**)&h->d_seg_beam, 4 * cap));
-  GM_TRY(hipMalloc((void**)&h->d_tops, 4 * (GM_SCAN_TILE + 1)));
-  GM_TRY(hipMalloc((void**)&h->d_centres, 12 * (size_t)ORBFE_GRIDMAP_MAX_KEYFRAMES));
-  GM_TRY(hipMalloc((void**)&h->d_kf, 16 * (size_t)ORBFE_GRIDMAP_MAX_KEYFRAMES));
-  GM_TRY(hipMalloc((void**)&h->d_stat, 8 * GM_ST_N));
-  GM_TRY(hipHostMalloc((void**)&h->h_stat, 8 * GM_ST_N, hipHostMallocDefault));
-  GM_TRY(hipMalloc((void**)&h->d_prob, 4 * (size_t)GM_PROB_CHUNK));
-  GM_TRY(hipMemsetAsync(h->d_occupied, 0, 4 * pad, h->stream));
-  GM_TRY(hipMemsetAsync(h->d_visits, 0, 4 * pad, h->stream));
-  GM_TRY(hipMemsetAsync(h->d_grid, 0, pad, h->stream));
-  GM_TRY(hipStreamSynchronize(h->stream));
-#undef GM_TRY
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_occupied, 4 * pad));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_visits, 4 * pad));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_grid, pad));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_pos, 12 * (size_t)GM_GROUP));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_rec, 16 * (size_t)GM_GROUP));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_seg, 4 * (size_t)GM_GROUP));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_seg_xy, 8 * cap));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_seg_err, 8 * cap));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_seg_beam, 4 * cap));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_tops, 4 * (GM_SCAN_TILE + 1)));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_centres, 12 * (size_t)ORBFE_GRIDMAP_MAX_KEYFRAMES));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_kf, 16 * (size_t)ORBFE_GRIDMAP_MAX_KEYFRAMES));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_stat, 8 * GM_ST_N));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipHostMalloc((void**)&h->h_stat, 8 * GM_ST_N, hipHostMallocDefault));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMalloc((void**)&h->d_prob, 4 * (size_t)GM_PROB_CHUNK));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMemsetAsync(h->d_occupied, 0, 4 * pad, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMemsetAsync(h->d_visits, 0, 4 * pad, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipMemsetAsync(h->d_grid, 0, pad, h->stream));
+  ORBFE_CREATE_HIP(h, orbfe_gridmap_destroy, hipStreamSynchronize(h->stream));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_gridmap_destroy(orbfe_gridmap* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+  if (orbfe_dev_close(h)) {
     hipFree(h->d_occupied);
     hipFree(h->d_visits);
     hipFree(h->d_grid);
@@ -503,7 +486,6 @@ extern "C" int orbfe_gridmap_destroy(orbfe_gridmap* h) {
     hipFree(h->d_stat);
     hipFree(h->d_prob);
     if (h->h_stat) hipHostFree(h->h_stat);
-    if (h->stream) hipStreamDestroy(h->stream);
   }
   delete h;
   return ORBFE_OK;

@@ -29,35 +29,13 @@
 #include "orbfe_device.h"
 #include "orbfe_init_core.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_stage.h"
 
 static_assert(INIT_FLAG_TOO_FEW == ORBFE_INIT_FLAG_TOO_FEW && INIT_FLAG_NO_MODEL == ORBFE_INIT_FLAG_NO_MODEL,
               "flag values");
 static_assert(INIT_MODEL_H == ORBFE_INIT_MODEL_H && INIT_MODEL_F == ORBFE_INIT_MODEL_F, "model values");
 
 #define INIT_HYP_THREADS 64
-
-// What k_init_select, k_init_checkrt and k_init_decide leave per problem (in the result buffer)
-struct InitSel {
-  int best_h, best_f, model, n_motions, candidate, n_inl;
-  unsigned flags;
-  int pad;
-  int n_good[8];
-  float cosv[8];
-  float SH, SF, RH, pad1;
-  float H21[9], F21[9];
-  float R[72], t[24];
-};
-
-// One launched problem, as the kernels see it. in_* are byte offsets into the upload buffer, o_*
-// into the result buffer, w_* into the workspace.
-struct InitDev {
-  int n1, n2, N, n_hyp, words, pad0, pad1, pad2;
-  float k[4];
-  float sigma, inv_sigma2, th2, pad3;
-  unsigned long long in_k1, in_k2, in_m1, in_m2, in_rand;
-  unsigned long long o_nrm, o_sh, o_sf, o_sel, o_mh, o_mf, o_p3d, o_tri;
-  unsigned long long w_models, w_masks, w_p3d, w_good, w_cos;
-};
 
 __device__ __forceinline__ float init_lane(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -389,27 +367,11 @@ __global__ __launch_bounds__(256) void k_init_decide(const uint8_t* __restrict__
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_init {
-  int device = -1;
+struct orbfe_init : OrbfeDev {
   int S = 0, Kmax = 0, M = 0, H = 0;
-  hipStream_t stream = nullptr;
-  uint8_t *d_in = nullptr, *h_in = nullptr, *d_res = nullptr, *h_res = nullptr, *d_ws = nullptr;
-  size_t in_bytes = 0, res_bytes = 0, ws_bytes = 0;
+  // inputs (one upload), results (one copy back), the workspace (device only); sized by init_plan_bounds
+  OrbfeStage in, res, ws;
 };
-
-static size_t init_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t init_in_bytes(size_t keys, size_t m, size_t e) {
-  return 2 * init_al(8 * keys) + 2 * init_al(4 * m) + init_al(32 * e);
-}
-static size_t init_res_bytes(size_t keys, size_t m, size_t e) {
-  const size_t w = (m + 63) / 64;
-  return init_al(2 * sizeof(InitNorm)) + 2 * init_al(4 * e) + init_al(sizeof(InitSel)) + 2 * init_al(8 * w) +
-         init_al(12 * keys) + init_al(keys);
-}
-static size_t init_ws_bytes(size_t keys, size_t m, size_t e) {
-  const size_t w = (m + 63) / 64;
-  return init_al(108 * e) + init_al(16 * w * e) + init_al(96 * keys) + init_al(8 * keys) + init_al(32 * m);
-}
 
 extern "C" int orbfe_init_create(int device, int max_problems, int max_keys, int max_matches, int max_hyp,
                                  orbfe_init** out) {
@@ -430,48 +392,26 @@ extern "C" int orbfe_init_create(int device, int max_problems, int max_keys, int
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_init_create: no such HIP device");
-  }
-  h->device = device;
-  h->in_bytes = init_al(sizeof(InitDev) * (size_t)h->S) + (size_t)h->S * init_in_bytes(h->Kmax, h->M, h->H);
-  h->res_bytes = (size_t)h->S * init_res_bytes(h->Kmax, h->M, h->H);
-  h->ws_bytes = (size_t)h->S * init_ws_bytes(h->Kmax, h->M, h->H);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int st = orbfe_dev_open(h, device, "orbfe_init_create");
+  if (st != ORBFE_OK) {
     orbfe_init_destroy(h);
     return st;
-  };
-#define INIT_TRY(expr)                            \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  INIT_TRY(hipSetDevice(device));
-  INIT_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  INIT_TRY(hipMalloc(&h->d_in, h->in_bytes));
-  INIT_TRY(hipMalloc(&h->d_res, h->res_bytes));
-  INIT_TRY(hipMalloc(&h->d_ws, h->ws_bytes));
-  INIT_TRY(hipHostMalloc(&h->h_in, h->in_bytes, hipHostMallocDefault));
-  INIT_TRY(hipHostMalloc(&h->h_res, h->res_bytes, hipHostMallocDefault));
-#undef INIT_TRY
+  }
+  size_t in_bytes, res_bytes, ws_bytes;
+  init_plan_bounds(h->S, h->Kmax, h->M, h->H, &in_bytes, &res_bytes, &ws_bytes);
+  ORBFE_CREATE_HIP(h, orbfe_init_destroy, orbfe_stage_alloc(&h->in, in_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_init_destroy, orbfe_stage_alloc(&h->res, res_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_init_destroy, orbfe_stage_alloc(&h->ws, ws_bytes, false));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_init_destroy(orbfe_init* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_in);
-    hipFree(h->d_res);
-    hipFree(h->d_ws);
-    if (h->h_in) hipHostFree(h->h_in);
-    if (h->h_res) hipHostFree(h->h_res);
-    if (h->stream) hipStreamDestroy(h->stream);
+  if (orbfe_dev_close(h)) {
+    orbfe_stage_free(&h->in);
+    orbfe_stage_free(&h->res);
+    orbfe_stage_free(&h->ws);
   }
   delete h;
   return ORBFE_OK;
@@ -506,13 +446,9 @@ static int init_check_problem(const orbfe_init* h, const orbfe_init_problem_t* p
     return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_init_solve_batch: result capacity below n_hyp or ceil(N / 64)");
   if (N < 8) return ORBFE_OK;  // ORBFE_INIT_FLAG_TOO_FEW: not launched, the draws are not read
   if (p->n_hyp > 0 && !p->rand_idx) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_init_solve_batch: null rand_idx");
-  for (int k = 0; k < p->n_hyp; k++)
-    for (int j = 0; j < 8; j++) {
-      const int d = p->rand_idx[8 * (size_t)k + j];
-      if (d < 0 || d > N - 1 - j)
-        return orbfe_set_error(ORBFE_ERR_ARG,
-                               "orbfe_init_solve_batch: rand_idx outside 0 .. N-1-j for draw j of its iteration");
-    }
+  if (!ransac_check_draws(p->rand_idx, p->n_hyp, 8, N))
+    return orbfe_set_error(ORBFE_ERR_ARG,
+                           "orbfe_init_solve_batch: rand_idx outside 0 .. N-1-j for draw j of its iteration");
   return ORBFE_OK;
 }
 
@@ -532,8 +468,10 @@ extern "C" int orbfe_init_solve_batch(orbfe_init* h, const orbfe_init_problem_t*
   for (int i = 0; i < n; i++)
     if (N[i] >= 8) act.push_back(i);
   const int na = (int)act.size();
-  InitDev* dev = reinterpret_cast<InitDev*>(h->h_in);
-  size_t in_off = init_al(sizeof(InitDev) * (size_t)std::max(na, 1)), res_off = 0, ws_off = 0;
+  OrbfeStage &in = h->in, &res = h->res, &ws = h->ws;
+  in.off = res.off = ws.off = 0;
+  InitDev* dev;
+  in.take<InitDev>((size_t)std::max(na, 1), &dev);
   int max_e = 0;
   for (int a = 0; a < na; a++) {
     const orbfe_init_problem_t& p = problems[act[a]];
@@ -545,49 +483,27 @@ extern "C" int orbfe_init_solve_batch(orbfe_init* h, const orbfe_init_problem_t*
     d.sigma = p.sigma;
     d.inv_sigma2 = (float)(1.0 / (double)(p.sigma * p.sigma));  // 1.0 / (sigma * sigma) (:335, :411)
     d.th2 = (float)(4.0 * (double)(p.sigma * p.sigma));         // 4.0 * mSigma2 into CheckRT's float th2
-    auto take = [](size_t& off, size_t bytes) {
-      const size_t o = off;
-      off += init_al(bytes);
-      return o;
-    };
-    const size_t w = (size_t)d.words;
-    d.in_k1 = take(in_off, 8 * n1);
-    d.in_k2 = take(in_off, 8 * n2);
-    d.in_m1 = take(in_off, 4 * m);
-    d.in_m2 = take(in_off, 4 * m);
-    d.in_rand = take(in_off, 32 * e);
-    d.o_nrm = take(res_off, 2 * sizeof(InitNorm));
-    d.o_sh = take(res_off, 4 * e);
-    d.o_sf = take(res_off, 4 * e);
-    d.o_sel = take(res_off, sizeof(InitSel));
-    d.o_mh = take(res_off, 8 * w);
-    d.o_mf = take(res_off, 8 * w);
-    d.o_p3d = take(res_off, 12 * n1);
-    d.o_tri = take(res_off, n1);
-    d.w_models = take(ws_off, 108 * e);
-    d.w_masks = take(ws_off, 16 * w * e);
-    d.w_p3d = take(ws_off, 96 * n1);
-    d.w_good = take(ws_off, 8 * n1);
-    d.w_cos = take(ws_off, 32 * m);
-    if (in_off > h->in_bytes || res_off > h->res_bytes || ws_off > h->ws_bytes)  // cannot happen within the bounds
+    init_layout(in, res, ws, n1, n2, m, e, d);
+    if (in.off > in.cap || res.off > res.cap || ws.off > ws.cap)  // cannot happen within the bounds
       return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_init_solve_batch: staging plan exceeds the handle's buffers");
-    memcpy(h->h_in + d.in_k1, p.keys1, 8 * n1);
-    memcpy(h->h_in + d.in_k2, p.keys2, 8 * n2);
-    int32_t* m1 = reinterpret_cast<int32_t*>(h->h_in + d.in_m1);
-    int32_t* m2 = reinterpret_cast<int32_t*>(h->h_in + d.in_m2);
+    memcpy(in.h + d.in_k1, p.keys1, 8 * n1);
+    memcpy(in.h + d.in_k2, p.keys2, 8 * n2);
+    int32_t* m1 = reinterpret_cast<int32_t*>(in.h + d.in_m1);
+    int32_t* m2 = reinterpret_cast<int32_t*>(in.h + d.in_m2);
     size_t c = 0;
     for (int i = 0; i < p.n1; i++)  // mvMatches12 (:54-63)
       if (p.matches12[i] >= 0) m1[c] = i, m2[c] = p.matches12[i], c++;
-    if (e) memcpy(h->h_in + d.in_rand, p.rand_idx, 32 * e);
+    if (e) memcpy(in.h + d.in_rand, p.rand_idx, 32 * e);
     dev[a] = d;
     max_e = std::max(max_e, p.n_hyp);
   }
   if (na > 0) {
     ORBFE_HIP_CHECK(hipSetDevice(h->device));
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->d_in, h->h_in, in_off, hipMemcpyHostToDevice, h->stream));
-    const uint8_t* din = h->d_in;
-    uint8_t* dres = h->d_res;
-    uint8_t* dws = h->d_ws;
+    int st;
+    if ((st = orbfe_stage_upload(&in, h->stream)) != ORBFE_OK) return st;
+    const uint8_t* din = in.d;
+    uint8_t* dres = res.d;
+    uint8_t* dws = ws.d;
     ORBFE_LAUNCH("k_init_normalize", k_init_normalize, dim3(na), dim3(128), 0, h->stream, din, dres);
     if (max_e > 0) {
       ORBFE_LAUNCH("k_init_hypotheses", k_init_hypotheses,
@@ -598,9 +514,7 @@ extern "C" int orbfe_init_solve_batch(orbfe_init* h, const orbfe_init_problem_t*
     ORBFE_LAUNCH("k_init_select", k_init_select, dim3(na), dim3(64), 0, h->stream, din, dres, (const uint8_t*)dws);
     ORBFE_LAUNCH("k_init_checkrt", k_init_checkrt, dim3(8, na), dim3(64), 0, h->stream, din, dres, dws);
     ORBFE_LAUNCH("k_init_decide", k_init_decide, dim3(na), dim3(256), 0, h->stream, din, dres, (const uint8_t*)dws);
-    ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, res_off, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if ((st = orbfe_stage_download(&res, h->stream)) != ORBFE_OK) return st;
   }
   for (int i = 0; i < n; i++) {
     orbfe_init_result_t& r = results[i];
@@ -630,13 +544,13 @@ extern "C" int orbfe_init_solve_batch(orbfe_init* h, const orbfe_init_problem_t*
   for (int a = 0; a < na; a++) {
     const InitDev& d = dev[a];
     orbfe_init_result_t& r = results[act[a]];
-    const uint8_t* base = h->h_res;
+    const uint8_t* base = res.h;
     const InitSel& S = *reinterpret_cast<const InitSel*>(base + d.o_sel);
     const size_t e = (size_t)d.n_hyp;
     if (r.score_h) memcpy(r.score_h, base + d.o_sh, 4 * e);
     if (r.score_f) memcpy(r.score_f, base + d.o_sf, 4 * e);
-    if (r.mask_h) memcpy(r.mask_h, base + d.o_mh, 8 * (size_t)d.words);
-    if (r.mask_f) memcpy(r.mask_f, base + d.o_mf, 8 * (size_t)d.words);
+    if (r.mask_h) orbfe_unpack_masks(r.mask_h, r.mask_words, base + d.o_mh, d.words, 1);
+    if (r.mask_f) orbfe_unpack_masks(r.mask_f, r.mask_words, base + d.o_mf, d.words, 1);
     r.flags = S.flags;
     r.sh = S.SH, r.sf = S.SF, r.rh = S.RH;
     r.model = S.model;

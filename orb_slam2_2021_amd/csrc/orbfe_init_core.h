@@ -21,6 +21,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "orbfe_stage.h"
 #include "orbfe_triangulate_core.h"
 
 #define INIT_HD __host__ __device__
@@ -588,4 +589,66 @@ INIT_HD inline int init_decide_h(const int* n_good, int n_inl) {
   }
   const bool ok = (double)second < 0.75 * (double)best && best > 50 && (double)best > 0.9 * (double)n_inl;
   return ok ? idx : -1;
+}
+
+// ------------------------------------------------------------------------------------------
+// staging (host)
+
+// What k_init_select, k_init_checkrt and k_init_decide leave per problem (in the result buffer)
+struct InitSel {
+  int best_h, best_f, model, n_motions, candidate, n_inl;
+  unsigned flags;
+  int pad;
+  int n_good[8];
+  float cosv[8];
+  float SH, SF, RH, pad1;
+  float H21[9], F21[9];
+  float R[72], t[24];
+};
+
+// One launched problem, as the kernels see it. in_* are byte offsets into the upload buffer, o_*
+// into the result buffer, w_* into the workspace.
+struct InitDev {
+  int n1, n2, N, n_hyp, words, pad0, pad1, pad2;
+  float k[4];
+  float sigma, inv_sigma2, th2, pad3;
+  unsigned long long in_k1, in_k2, in_m1, in_m2, in_rand;
+  unsigned long long o_nrm, o_sh, o_sf, o_sel, o_mh, o_mf, o_p3d, o_tri;
+  unsigned long long w_models, w_masks, w_p3d, w_good, w_cos;
+};
+
+// The arrays of one problem with n1 and n2 keypoints, m matches and e hypotheses, taken from the three
+// blocks in the order the buffers hold them; fills d's offsets only. The one statement of the buffer
+// plan: over counting blocks it sizes a handle (init_plan_bounds), over the real ones it places a solve.
+inline void init_layout(OrbfeStage& in, OrbfeStage& res, OrbfeStage& ws, size_t n1, size_t n2, size_t m, size_t e,
+                        InitDev& d) {
+  const size_t w = (m + 63) / 64;
+  d.in_k1 = in.take(8 * n1);
+  d.in_k2 = in.take(8 * n2);
+  d.in_m1 = in.take(4 * m);
+  d.in_m2 = in.take(4 * m);
+  d.in_rand = in.take(32 * e);
+  d.o_nrm = res.take(2 * sizeof(InitNorm));
+  d.o_sh = res.take(4 * e);
+  d.o_sf = res.take(4 * e);
+  d.o_sel = res.take(sizeof(InitSel));
+  d.o_mh = res.take(8 * w);
+  d.o_mf = res.take(8 * w);
+  d.o_p3d = res.take(12 * n1);
+  d.o_tri = res.take(n1);
+  d.w_models = ws.take(108 * e);
+  d.w_masks = ws.take(16 * w * e);
+  d.w_p3d = ws.take(96 * n1);
+  d.w_good = ws.take(8 * n1);
+  d.w_cos = ws.take(32 * m);
+}
+
+// A handle's buffer sizes: the record table and S problems at the bounds
+inline void init_plan_bounds(size_t S, size_t K, size_t M, size_t H, size_t* in_bytes, size_t* res_bytes,
+                             size_t* ws_bytes) {
+  OrbfeStage in, res, ws;
+  InitDev d;
+  in.take(sizeof(InitDev) * S);
+  for (size_t s = 0; s < S; s++) init_layout(in, res, ws, K, K, M, H, d);
+  *in_bytes = in.off, *res_bytes = res.off, *ws_bytes = ws.off;
 }

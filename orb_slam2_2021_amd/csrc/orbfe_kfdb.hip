@@ -35,6 +35,7 @@
 #include "../../include/orbfe_kfdb.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_stage.h"
 
 #define KFDB_SWEEP_THREADS 256
 #define KFDB_FIN_THREADS 1024
@@ -326,8 +327,7 @@ __global__ __launch_bounds__(KFDB_FIN_THREADS) void k_kfdb_finish(KfdbFinishArgs
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_kfdb {
-  int device = -1;
+struct orbfe_kfdb : OrbfeDev {
   int n_words = 0;
   int M = 0, W = 0;
   // bookkeeping (also on a host-only handle)
@@ -341,7 +341,6 @@ struct orbfe_kfdb {
   uint32_t next_pos = 0;  // < 2M
   bool neigh_dirty = true;
   // device
-  hipStream_t stream = nullptr;
   hipEvent_t ev = nullptr;
   KfdbStore st{};
   int32_t* d_neigh = nullptr;      // [M * 10]
@@ -359,7 +358,6 @@ struct orbfe_kfdb {
   std::vector<int32_t> neigh_host;
 };
 
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static void kfdb_reset_host(orbfe_kfdb* db) {
   db->slot_of.clear();
@@ -397,63 +395,48 @@ extern "C" int orbfe_kfdb_create(const orbfe_vocabulary* voc, int max_keyframes,
     *out = db;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete db;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_kfdb_create: no such HIP device");
+  const int open_st = orbfe_dev_open(db, device, "orbfe_kfdb_create");
+  if (open_st != ORBFE_OK) {
+    orbfe_kfdb_destroy(db);
+    return open_st;
   }
-  db->device = device;
   const size_t M = (size_t)db->M, W = (size_t)db->W;
   // staging: a query (words, weights, excluded slots) or a host add (words, weights, count) or
   // a device batch (slots, positions, counts back)
-  db->stage_bytes = al256(4 * (size_t)ORBFE_KFDB_MAX_WORDS) + al256(8 * (size_t)ORBFE_KFDB_MAX_WORDS) +
-                    3 * al256(4 * M) + 256;
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
-    orbfe_kfdb_destroy(db);
-    return st;
-  };
-#define KFDB_TRY(expr)                                \
-  do {                                                \
-    hipError_t _e = (expr);                           \
-    if (_e != hipSuccess) return fail(_e, #expr);     \
-  } while (0)
-  KFDB_TRY(hipSetDevice(device));
-  KFDB_TRY(hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking));
-  KFDB_TRY(hipEventCreateWithFlags(&db->ev, hipEventDisableTiming));
-  KFDB_TRY(hipMalloc(&db->st.words, 4 * M * W));
-  KFDB_TRY(hipMalloc(&db->st.weights, 8 * M * W));
-  KFDB_TRY(hipMalloc(&db->st.n, 4 * M));
-  KFDB_TRY(hipMalloc(&db->st.pos, 4 * M));
-  KFDB_TRY(hipMalloc(&db->st.slot_at_pos, 4 * 2 * M));
-  KFDB_TRY(hipMalloc(&db->st.reloc, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_neigh, 4 * M * KFDB_NEIGH));
-  KFDB_TRY(hipMalloc(&db->d_common, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_first, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_si, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_first_idx, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_acc, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_best, 4 * M));
-  KFDB_TRY(hipMalloc(&db->d_res, 4 * (4 + 5 * M)));
-  KFDB_TRY(hipHostMalloc(&db->h_res, 4 * (4 + 5 * M), hipHostMallocDefault));
-  KFDB_TRY(hipMalloc(&db->d_stage, db->stage_bytes));
-  KFDB_TRY(hipHostMalloc(&db->h_stage, db->stage_bytes, hipHostMallocDefault));
-  KFDB_TRY(hipMemsetAsync(db->st.n, 0xff, 4 * M, db->stream));
-  KFDB_TRY(hipMemsetAsync(db->st.slot_at_pos, 0, 4 * 2 * M, db->stream));
+  db->stage_bytes = orbfe_al256(4 * (size_t)ORBFE_KFDB_MAX_WORDS) + orbfe_al256(8 * (size_t)ORBFE_KFDB_MAX_WORDS) +
+                    3 * orbfe_al256(4 * M) + 256;
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipEventCreateWithFlags(&db->ev, hipEventDisableTiming));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->st.words, 4 * M * W));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->st.weights, 8 * M * W));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->st.n, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->st.pos, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->st.slot_at_pos, 4 * 2 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->st.reloc, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_neigh, 4 * M * KFDB_NEIGH));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_common, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_first, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_si, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_first_idx, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_acc, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_best, 4 * M));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_res, 4 * (4 + 5 * M)));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipHostMalloc(&db->h_res, 4 * (4 + 5 * M), hipHostMallocDefault));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMalloc(&db->d_stage, db->stage_bytes));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipHostMalloc(&db->h_stage, db->stage_bytes, hipHostMallocDefault));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMemsetAsync(db->st.n, 0xff, 4 * M, db->stream));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipMemsetAsync(db->st.slot_at_pos, 0, 4 * 2 * M, db->stream));
   // k_kfdb_finish sorts up to 16384 64-bit keys in LDS (128 KiB of the CU's 160 KiB)
-  KFDB_TRY(hipFuncSetAttribute((const void*)k_kfdb_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               8 * ORBFE_KFDB_MAX_KEYFRAMES));
-  KFDB_TRY(hipStreamSynchronize(db->stream));
-#undef KFDB_TRY
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy,
+                   hipFuncSetAttribute((const void*)k_kfdb_finish, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       8 * ORBFE_KFDB_MAX_KEYFRAMES));
+  ORBFE_CREATE_HIP(db, orbfe_kfdb_destroy, hipStreamSynchronize(db->stream));
   *out = db;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_kfdb_destroy(orbfe_kfdb* db) {
   if (!db) return ORBFE_OK;
-  if (db->device >= 0) {
-    hipSetDevice(db->device);
-    if (db->stream) hipStreamSynchronize(db->stream);
+  if (orbfe_dev_close(db)) {
     hipFree(db->st.words);
     hipFree(db->st.weights);
     hipFree(db->st.n);
@@ -472,7 +455,6 @@ extern "C" int orbfe_kfdb_destroy(orbfe_kfdb* db) {
     if (db->h_res) hipHostFree(db->h_res);
     if (db->h_stage) hipHostFree(db->h_stage);
     if (db->ev) hipEventDestroy(db->ev);
-    if (db->stream) hipStreamDestroy(db->stream);
   }
   delete db;
   return ORBFE_OK;
@@ -546,8 +528,8 @@ extern "C" int orbfe_kfdb_add(orbfe_kfdb* db, int64_t kf_id, const uint32_t* wor
   if (db->device >= 0) {
     hipSetDevice(db->device);
     // staging: words | weights | {slot, pos, n, count back}
-    const size_t o_w = 0, o_v = al256(4 * (size_t)ORBFE_KFDB_MAX_WORDS);
-    const size_t o_m = o_v + al256(8 * (size_t)ORBFE_KFDB_MAX_WORDS);
+    const size_t o_w = 0, o_v = orbfe_al256(4 * (size_t)ORBFE_KFDB_MAX_WORDS);
+    const size_t o_m = o_v + orbfe_al256(8 * (size_t)ORBFE_KFDB_MAX_WORDS);
     if (n > 0) {
       memcpy(db->h_stage + o_w, words, 4 * (size_t)n);
       memcpy(db->h_stage + o_v, weights, 8 * (size_t)n);
@@ -609,7 +591,7 @@ extern "C" int orbfe_kfdb_add_batch_device(orbfe_kfdb* db, int n, const int64_t*
   int st = kfdb_reserve_positions(db, n);
   if (st) return st;
   // staging: slots | positions | counts back (each n <= M ints)
-  const size_t b = al256(4 * (size_t)db->M);
+  const size_t b = orbfe_al256(4 * (size_t)db->M);
   int32_t* hs = reinterpret_cast<int32_t*>(db->h_stage);
   int32_t* hp = reinterpret_cast<int32_t*>(db->h_stage + b);
   int32_t* hc = reinterpret_cast<int32_t*>(db->h_stage + 2 * b);
@@ -724,8 +706,8 @@ extern "C" int orbfe_kfdb_query(orbfe_kfdb* db, const orbfe_kfdb_query_t* q, orb
   if (hi == 0 || q->n == 0) return ORBFE_OK;  // nothing can share a word
   hipSetDevice(db->device);
   // staging: words | weights | excluded slots
-  const size_t o_w = 0, o_v = al256(4 * (size_t)ORBFE_KFDB_MAX_WORDS);
-  const size_t o_x = o_v + al256(8 * (size_t)ORBFE_KFDB_MAX_WORDS);
+  const size_t o_w = 0, o_v = orbfe_al256(4 * (size_t)ORBFE_KFDB_MAX_WORDS);
+  const size_t o_x = o_v + orbfe_al256(8 * (size_t)ORBFE_KFDB_MAX_WORDS);
   int32_t* hx = reinterpret_cast<int32_t*>(db->h_stage + o_x);
   int n_excl = 0;
   if (q->mode == ORBFE_KFDB_LOOP) {

@@ -112,10 +112,8 @@ __global__ __launch_bounds__(BA_BLOCK) void k_lba_classify(LbaWs w, uint8_t* fla
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_lba {
-  int device = -1;
+struct orbfe_lba : OrbfeDev {
   int max_free = 0, max_kf = 0, max_points = 0, max_edges = 0;
-  hipStream_t stream = nullptr;
   uint8_t* d_pool = nullptr;
   size_t pool_bytes = 0;
   LmRec* h_rec = nullptr;  // pinned
@@ -125,7 +123,8 @@ struct orbfe_lba {
 
 // carves the device pool; with base == nullptr only the size is computed
 static size_t lba_carve(orbfe_lba* h, uint8_t* base) {
-  BaPool pool = {base};
+  OrbfeStage pool;
+  pool.d = base;
   ba_carve(pool, h->w, h->max_kf, h->max_free, h->max_points, h->max_edges, true);
   pool.take(h->d_flag, h->max_edges);
   return pool.off;
@@ -146,28 +145,14 @@ extern "C" int orbfe_lba_create(int device, int max_free_kf, int max_kf, int max
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_lba_create: no such HIP device");
-  }
-  h->device = device;
-  h->pool_bytes = lba_carve(h, nullptr);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int open_st = orbfe_dev_open(h, device, "orbfe_lba_create");
+  if (open_st != ORBFE_OK) {
     orbfe_lba_destroy(h);
-    return st;
-  };
-#define LBA_TRY(expr)                             \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  LBA_TRY(hipSetDevice(device));
-  LBA_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  LBA_TRY(hipMalloc(&h->d_pool, h->pool_bytes));
-  LBA_TRY(hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
-#undef LBA_TRY
+    return open_st;
+  }
+  h->pool_bytes = lba_carve(h, nullptr);
+  ORBFE_CREATE_HIP(h, orbfe_lba_destroy, hipMalloc(&h->d_pool, h->pool_bytes));
+  ORBFE_CREATE_HIP(h, orbfe_lba_destroy, hipHostMalloc(&h->h_rec, sizeof(LmRec), hipHostMallocDefault));
   lba_carve(h, h->d_pool);
   *out = h;
   return ORBFE_OK;
@@ -175,12 +160,9 @@ extern "C" int orbfe_lba_create(int device, int max_free_kf, int max_kf, int max
 
 extern "C" int orbfe_lba_destroy(orbfe_lba* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
+  if (orbfe_dev_close(h)) {
     hipFree(h->d_pool);
     if (h->h_rec) hipHostFree(h->h_rec);
-    if (h->stream) hipStreamDestroy(h->stream);
   }
   delete h;
   return ORBFE_OK;

@@ -25,6 +25,7 @@
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
 #include "orbfe_mapcorr_core.h"
+#include "orbfe_stage.h"
 
 #define MC_BLOCK 256
 
@@ -66,37 +67,9 @@ __global__ __launch_bounds__(MC_BLOCK) void k_mc_gba_point(McGba w) {
 // ------------------------------------------------------------------------------------------
 // host
 
-namespace {
-size_t mc_al(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// A block that exists on the host (pinned) and on the device at the same offsets
-struct McBlock {
-  uint8_t* h = nullptr;
-  uint8_t* d = nullptr;
-  size_t cap = 0, off = 0;
-  // reserves count elements; *host receives the host address, the device address is returned
-  template <class T>
-  T* take(size_t count, T** host) {
-    const size_t at = off;
-    off += mc_al(sizeof(T) * count);
-    if (host) *host = reinterpret_cast<T*>(h + at);
-    return reinterpret_cast<T*>(d + at);
-  }
-  template <class T>
-  const T* put(const T* src, size_t count) {
-    T* host;
-    T* dev = take<T>(count, &host);
-    if (count) memcpy(host, src, sizeof(T) * count);
-    return dev;
-  }
-};
-}  // namespace
-
-struct orbfe_mapcorr {
-  int device = -1;
+struct orbfe_mapcorr : OrbfeDev {
   int max_kf = 0, max_points = 0, max_edges = 0;
-  hipStream_t stream = nullptr;
-  McBlock in, out;         // inputs (one upload), outputs (one copy back)
+  OrbfeStage in, out;      // inputs (one upload), outputs (one copy back)
   uint8_t* d_work = nullptr;  // device only: the old and new centres, the inverses
   size_t work_bytes = 0;
 };
@@ -183,17 +156,6 @@ void mc_unpack_normals(const McNormalsHost& host, int n_points, const orbfe_mapc
   }
 }
 
-int mc_upload(orbfe_mapcorr* h) {
-  if (h->in.off > 0) ORBFE_HIP_CHECK(hipMemcpyAsync(h->in.d, h->in.h, h->in.off, hipMemcpyHostToDevice, h->stream));
-  return ORBFE_OK;
-}
-
-int mc_download(orbfe_mapcorr* h) {
-  ORBFE_HIP_CHECK(hipGetLastError());
-  if (h->out.off > 0) ORBFE_HIP_CHECK(hipMemcpyAsync(h->out.h, h->out.d, h->out.off, hipMemcpyDeviceToHost, h->stream));
-  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
-  return ORBFE_OK;
-}
 }  // namespace
 
 extern "C" int orbfe_mapcorr_create(int device, int max_kf, int max_points, int max_edges, orbfe_mapcorr** out) {
@@ -208,48 +170,25 @@ extern "C" int orbfe_mapcorr_create(int device, int max_kf, int max_points, int 
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_mapcorr_create: no such HIP device");
-  }
-  h->device = device;
-  h->in.cap = mc_in_bytes(max_kf, max_points, max_edges);
-  h->out.cap = mc_out_bytes(max_kf, max_points);
-  h->work_bytes = mc_work_bytes(max_kf);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int open_st = orbfe_dev_open(h, device, "orbfe_mapcorr_create");
+  if (open_st != ORBFE_OK) {
     orbfe_mapcorr_destroy(h);
-    return st;
-  };
-#define MC_TRY(expr)                              \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  MC_TRY(hipSetDevice(device));
-  MC_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  MC_TRY(hipMalloc(&h->in.d, h->in.cap));
-  MC_TRY(hipMalloc(&h->out.d, h->out.cap));
-  MC_TRY(hipMalloc(&h->d_work, h->work_bytes));
-  MC_TRY(hipHostMalloc(&h->in.h, h->in.cap, hipHostMallocDefault));
-  MC_TRY(hipHostMalloc(&h->out.h, h->out.cap, hipHostMallocDefault));
-#undef MC_TRY
+    return open_st;
+  }
+  h->work_bytes = mc_work_bytes(max_kf);
+  ORBFE_CREATE_HIP(h, orbfe_mapcorr_destroy, orbfe_stage_alloc(&h->in, mc_in_bytes(max_kf, max_points, max_edges), true));
+  ORBFE_CREATE_HIP(h, orbfe_mapcorr_destroy, orbfe_stage_alloc(&h->out, mc_out_bytes(max_kf, max_points), true));
+  ORBFE_CREATE_HIP(h, orbfe_mapcorr_destroy, hipMalloc(&h->d_work, h->work_bytes));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_mapcorr_destroy(orbfe_mapcorr* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->in.d);
-    hipFree(h->out.d);
+  if (orbfe_dev_close(h)) {
+    orbfe_stage_free(&h->in);
+    orbfe_stage_free(&h->out);
     hipFree(h->d_work);
-    if (h->in.h) hipHostFree(h->in.h);
-    if (h->out.h) hipHostFree(h->out.h);
-    if (h->stream) hipStreamDestroy(h->stream);
   }
   delete h;
   return ORBFE_OK;
@@ -275,10 +214,10 @@ extern "C" int orbfe_mapcorr_update_normal_depth(orbfe_mapcorr* h, const orbfe_m
   McNormalsHost host;
   nd.ow = h->in.put(p->ow, 3 * (size_t)p->n_kf);
   mc_pack_points(h, q, &nd, &d_xw, &d_bad, &host);
-  if ((st = mc_upload(h)) != ORBFE_OK) return st;
+  if ((st = orbfe_stage_upload(&h->in, h->stream)) != ORBFE_OK) return st;
   if (q.n_points > 0)
     ORBFE_LAUNCH("k_mc_normals", k_mc_normals, dim3(mc_grid(q.n_points)), dim3(MC_BLOCK), 0, h->stream, nd, d_xw, d_bad, q.n_points);
-  if ((st = mc_download(h)) != ORBFE_OK) return st;
+  if ((st = orbfe_stage_download(&h->out, h->stream)) != ORBFE_OK) return st;
   mc_unpack_normals(host, q.n_points, *r);
   return ORBFE_OK;
 }
@@ -334,14 +273,14 @@ extern "C" int orbfe_mapcorr_correct_loop(orbfe_mapcorr* h, const orbfe_mapcorr_
   w.tcw_out = h->out.take<float>(12 * nc, &h_tcw);
   w.xw_out = h->out.take<float>(3 * np, &h_xw);
   w.corrected_by = h->out.take<int>(np, &h_by);
-  McBlock work;
+  OrbfeStage work;
   work.d = h->d_work;
   w.ow_old = work.take<float>(3 * nk, nullptr);
   w.ow_new = work.take<float>(3 * nc, nullptr);
   w.swi = work.take<double>(8 * nc, nullptr);
   w.nd.ow = w.ow_old, w.nd.ow_new = w.ow_new;
 
-  if ((st = mc_upload(h)) != ORBFE_OK) return st;
+  if ((st = orbfe_stage_upload(&h->in, h->stream)) != ORBFE_OK) return st;
   ORBFE_LAUNCH("k_mc_centres", k_mc_centres, dim3(mc_grid(p->n_kf)), dim3(MC_BLOCK), 0, h->stream, w.tcw, w.ow_old, p->n_kf);
   ORBFE_LAUNCH("k_mc_loop_kf", k_mc_loop_kf, dim3(mc_grid(p->n_connected)), dim3(MC_BLOCK), 0, h->stream, w);
   if (np > 0) {
@@ -350,7 +289,7 @@ extern "C" int orbfe_mapcorr_correct_loop(orbfe_mapcorr* h, const orbfe_mapcorr_
       ORBFE_LAUNCH("k_mc_loop_mark", k_mc_loop_mark, dim3(mc_grid(p->n_slots)), dim3(MC_BLOCK), 0, h->stream, w);
     ORBFE_LAUNCH("k_mc_loop_point", k_mc_loop_point, dim3(mc_grid(q.n_points)), dim3(MC_BLOCK), 0, h->stream, w);
   }
-  if ((st = mc_download(h)) != ORBFE_OK) return st;
+  if ((st = orbfe_stage_download(&h->out, h->stream)) != ORBFE_OK) return st;
   memcpy(r->noncorrected_sim3, h_nonc, sizeof(double) * 8 * nc);
   memcpy(r->corrected_sim3, h_corr, sizeof(double) * 8 * nc);
   memcpy(r->tcw_out, h_tcw, sizeof(float) * 12 * nc);
@@ -402,19 +341,19 @@ extern "C" int orbfe_mapcorr_apply_gba(orbfe_mapcorr* h, const orbfe_mapcorr_gba
   w.tcw_out = h->out.take<float>(12 * nk, &h_tcw);
   w.xw_out = h->out.take<float>(3 * np, &h_xw);
   w.pt_changed = h->out.take<uint8_t>(np, &h_changed);
-  McBlock work;
+  OrbfeStage work;
   work.d = h->d_work;
   w.ow_out = work.take<float>(3 * nk, nullptr);
 
   int st;
-  if ((st = mc_upload(h)) != ORBFE_OK) return st;
+  if ((st = orbfe_stage_upload(&h->in, h->stream)) != ORBFE_OK) return st;
   const int levels = (int)plan.level_begin.size() - 1;
   for (int d = 0; d < levels; d++) {
     const int b = plan.level_begin[d], e = plan.level_begin[d + 1];
     if (e > b) ORBFE_LAUNCH("k_mc_gba_kf", k_mc_gba_kf, dim3(mc_grid(e - b)), dim3(MC_BLOCK), 0, h->stream, w, b, e);
   }
   if (np > 0) ORBFE_LAUNCH("k_mc_gba_point", k_mc_gba_point, dim3(mc_grid(p->n_points)), dim3(MC_BLOCK), 0, h->stream, w);
-  if ((st = mc_download(h)) != ORBFE_OK) return st;
+  if ((st = orbfe_stage_download(&h->out, h->stream)) != ORBFE_OK) return st;
   if (nk > 0) memcpy(r->tcw_out, h_tcw, sizeof(float) * 12 * nk);
   for (size_t k = 0; k < nk; k++) r->propagated[k] = p->optimised[k] ? 0 : 1;
   if (np > 0) {

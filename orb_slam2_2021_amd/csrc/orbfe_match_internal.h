@@ -14,6 +14,7 @@
 #include "../../include/orbfe.h"
 #include "../../include/orbfe_match_batch.h"
 #include "orbfe_device.h"
+#include "orbfe_stage.h"
 
 #define TH_HIGH 100
 #define TH_LOW 50
@@ -182,7 +183,7 @@ struct Arena {
   size_t total = 0;
   size_t add(size_t bytes) {
     const size_t off = total;
-    total += (bytes + 255) & ~(size_t)255;
+    total += orbfe_al256(bytes);
     return off;
   }
 };

@@ -29,20 +29,10 @@
 #include "orbfe_ktimer.h"
 #include "orbfe_lm_device.h"
 #include "orbfe_optsim3_core.h"
+#include "orbfe_stage.h"
 
 static_assert(ORBFE_OPTSIM3_MAX_OBS <= PO_LANES * 64, "a lane's removal flags are one 64-bit word");
 static_assert(sizeof(PoRound) == sizeof(orbfe_poseopt_round_t), "trace layout");
-
-// One problem as the kernel sees it. in_* are byte offsets into the upload buffer, o_* into the result
-// buffer.
-struct OsDev {
-  int n, fix_scale, has_kf2, pad;
-  double cam[9];    // k1, k2 (fx, fy, cx, cy: float widened to double), th2
-  float start[13];  // r12, t12, s12
-  float kf2[12];    // r2w, t2w
-  float pad2;
-  unsigned long long in_valid, in_p1, in_p2, in_kp1, in_kp2, in_is1, in_is2, o_out, o_mask;
-};
 
 __global__ __launch_bounds__(PO_LANES) void k_optsim3(const uint8_t* __restrict__ in, uint8_t* __restrict__ res) {
   const OsDev& D = reinterpret_cast<const OsDev*>(in)[blockIdx.x];
@@ -81,17 +71,10 @@ __global__ __launch_bounds__(PO_LANES) void k_optsim3(const uint8_t* __restrict_
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_optsim3 {
-  int device = -1;
+struct orbfe_optsim3 : OrbfeDev {
   int S = 0, C = 0;
-  hipStream_t stream = nullptr;
-  uint8_t *d_in = nullptr, *h_in = nullptr, *d_res = nullptr, *h_res = nullptr;
-  size_t in_bytes = 0, res_bytes = 0;
+  OrbfeStage in, res;  // inputs (one upload), results (one copy back); sized by os_plan_bounds
 };
-
-static size_t os_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t os_in_bytes(size_t n) { return os_al(n) + 2 * os_al(12 * n) + 2 * os_al(8 * n) + 2 * os_al(4 * n); }
-static size_t os_res_bytes(size_t n) { return os_al(sizeof(OsOut)) + os_al(8 * ((n + 63) / 64)); }
 
 extern "C" int orbfe_optsim3_create(int device, int max_problems, int max_obs, orbfe_optsim3** out) {
   if (!out) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_optsim3_create: bad argument");
@@ -105,45 +88,24 @@ extern "C" int orbfe_optsim3_create(int device, int max_problems, int max_obs, o
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_optsim3_create: no such HIP device");
-  }
-  h->device = device;
-  h->in_bytes = os_al(sizeof(OsDev) * (size_t)h->S) + (size_t)h->S * os_in_bytes(h->C);
-  h->res_bytes = (size_t)h->S * os_res_bytes(h->C);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int st = orbfe_dev_open(h, device, "orbfe_optsim3_create");
+  if (st != ORBFE_OK) {
     orbfe_optsim3_destroy(h);
     return st;
-  };
-#define OS_TRY(expr)                              \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  OS_TRY(hipSetDevice(device));
-  OS_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  OS_TRY(hipMalloc(&h->d_in, h->in_bytes));
-  OS_TRY(hipMalloc(&h->d_res, h->res_bytes));
-  OS_TRY(hipHostMalloc(&h->h_in, h->in_bytes, hipHostMallocDefault));
-  OS_TRY(hipHostMalloc(&h->h_res, h->res_bytes, hipHostMallocDefault));
-#undef OS_TRY
+  }
+  size_t in_bytes, res_bytes;
+  os_plan_bounds(h->S, h->C, &in_bytes, &res_bytes);
+  ORBFE_CREATE_HIP(h, orbfe_optsim3_destroy, orbfe_stage_alloc(&h->in, in_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_optsim3_destroy, orbfe_stage_alloc(&h->res, res_bytes, true));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_optsim3_destroy(orbfe_optsim3* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_in);
-    hipFree(h->d_res);
-    if (h->h_in) hipHostFree(h->h_in);
-    if (h->h_res) hipHostFree(h->h_res);
-    if (h->stream) hipStreamDestroy(h->stream);
+  if (orbfe_dev_close(h)) {
+    orbfe_stage_free(&h->in);
+    orbfe_stage_free(&h->res);
   }
   delete h;
   return ORBFE_OK;
@@ -170,8 +132,10 @@ extern "C" int orbfe_optsim3_batch(orbfe_optsim3* h, const orbfe_optsim3_problem
     if (st != ORBFE_OK) return st;
   }
   if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "Sim3 optimizer is host-only (device < 0)");
-  OsDev* dev = reinterpret_cast<OsDev*>(h->h_in);
-  size_t in_off = os_al(sizeof(OsDev) * (size_t)n_problems), res_off = 0;
+  OrbfeStage &in = h->in, &res = h->res;
+  in.off = res.off = 0;
+  OsDev* dev;
+  in.take<OsDev>((size_t)n_problems, &dev);
   for (int i = 0; i < n_problems; i++) {
     const orbfe_optsim3_problem_t& p = problems[i];
     const size_t n = (size_t)p.n;
@@ -189,47 +153,31 @@ extern "C" int orbfe_optsim3_batch(orbfe_optsim3* h, const orbfe_optsim3_problem
       memcpy(d.kf2, p.r2w, sizeof(p.r2w));
       memcpy(d.kf2 + 9, p.t2w, sizeof(p.t2w));
     }
-    auto take_in = [&](size_t bytes) {
-      const size_t o = in_off;
-      in_off += os_al(bytes);
-      return o;
-    };
-    d.in_valid = take_in(n);
-    d.in_p1 = take_in(12 * n);
-    d.in_p2 = take_in(12 * n);
-    d.in_kp1 = take_in(8 * n);
-    d.in_kp2 = take_in(8 * n);
-    d.in_is1 = take_in(4 * n);
-    d.in_is2 = take_in(4 * n);
-    d.o_out = res_off;
-    res_off += os_al(sizeof(OsOut));
-    d.o_mask = res_off;
-    res_off += os_al(8 * ((n + 63) / 64));
-    if (in_off > h->in_bytes || res_off > h->res_bytes)  // cannot happen within the bounds
+    os_layout(in, res, n, d);
+    if (in.off > in.cap || res.off > res.cap)  // cannot happen within the bounds
       return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_optsim3_batch: staging plan exceeds the handle's buffers");
     if (n > 0) {
-      memcpy(h->h_in + d.in_valid, p.valid, n);
-      memcpy(h->h_in + d.in_p1, p.p3d1c, 12 * n);
-      memcpy(h->h_in + d.in_p2, p.p3d2c, 12 * n);
-      memcpy(h->h_in + d.in_kp1, p.kp_un1, 8 * n);
-      memcpy(h->h_in + d.in_kp2, p.kp_un2, 8 * n);
-      memcpy(h->h_in + d.in_is1, p.inv_sigma2_1, 4 * n);
-      memcpy(h->h_in + d.in_is2, p.inv_sigma2_2, 4 * n);
+      memcpy(in.h + d.in_valid, p.valid, n);
+      memcpy(in.h + d.in_p1, p.p3d1c, 12 * n);
+      memcpy(in.h + d.in_p2, p.p3d2c, 12 * n);
+      memcpy(in.h + d.in_kp1, p.kp_un1, 8 * n);
+      memcpy(in.h + d.in_kp2, p.kp_un2, 8 * n);
+      memcpy(in.h + d.in_is1, p.inv_sigma2_1, 4 * n);
+      memcpy(in.h + d.in_is2, p.inv_sigma2_2, 4 * n);
     }
     dev[i] = d;
   }
   ORBFE_HIP_CHECK(hipSetDevice(h->device));
-  ORBFE_HIP_CHECK(hipMemcpyAsync(h->d_in, h->h_in, in_off, hipMemcpyHostToDevice, h->stream));
-  const uint8_t* din = h->d_in;
-  uint8_t* dres = h->d_res;
+  int st;
+  if ((st = orbfe_stage_upload(&in, h->stream)) != ORBFE_OK) return st;
+  const uint8_t* din = in.d;
+  uint8_t* dres = res.d;
   ORBFE_LAUNCH("k_optsim3", k_optsim3, dim3(n_problems), dim3(PO_LANES), 0, h->stream, din, dres);
-  ORBFE_HIP_CHECK(hipGetLastError());
-  ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, res_off, hipMemcpyDeviceToHost, h->stream));
-  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  if ((st = orbfe_stage_download(&res, h->stream)) != ORBFE_OK) return st;
   for (int i = 0; i < n_problems; i++) {
     const OsDev& d = dev[i];
     orbfe_optsim3_result_t& r = results[i];
-    const OsOut* o = reinterpret_cast<const OsOut*>(h->h_res + d.o_out);
+    const OsOut* o = reinterpret_cast<const OsOut*>(res.h + d.o_out);
     memcpy(r.sim3_q_t_s, o->sim3, sizeof(r.sim3_q_t_s));
     memcpy(r.s12_rt, o->s12_rt, sizeof(r.s12_rt));
     memcpy(r.scw, o->scw, sizeof(r.scw));
@@ -239,11 +187,7 @@ extern "C" int orbfe_optsim3_batch(orbfe_optsim3* h, const orbfe_optsim3_problem
     r.rounds_run = o->rounds_run;
     r.flags = o->flags;
     memcpy(r.rounds, o->rounds, sizeof(r.rounds));
-    if (r.removed_mask) {
-      const int words = (d.n + 63) / 64;
-      memcpy(r.removed_mask, h->h_res + d.o_mask, 8 * (size_t)words);
-      for (int w = words; w < r.mask_words; w++) r.removed_mask[w] = 0;
-    }
+    if (r.removed_mask) orbfe_unpack_masks(r.removed_mask, r.mask_words, res.h + d.o_mask, (d.n + 63) / 64, 1);
   }
   return ORBFE_OK;
 }

@@ -557,3 +557,41 @@ PO_HD inline void os_optimize(const G& g, const OsProblem& P, OsWork& w, OsOut* 
     o->pad = 0;
   }
 }
+
+// ------------------------------------------------------------------------------------------
+// staging (host)
+
+// One problem as the kernel sees it. in_* are byte offsets into the upload buffer, o_* into the result
+// buffer.
+struct OsDev {
+  int n, fix_scale, has_kf2, pad;
+  double cam[9];    // k1, k2 (fx, fy, cx, cy: float widened to double), th2
+  float start[13];  // r12, t12, s12
+  float kf2[12];    // r2w, t2w
+  float pad2;
+  unsigned long long in_valid, in_p1, in_p2, in_kp1, in_kp2, in_is1, in_is2, o_out, o_mask;
+};
+
+// The arrays of one problem with n correspondences, taken from the two blocks in the order the buffers
+// hold them; fills d's offsets only. The one statement of the buffer plan: over counting blocks it sizes
+// a handle (os_plan_bounds), over the real ones it places a batch.
+inline void os_layout(OrbfeStage& in, OrbfeStage& res, size_t n, OsDev& d) {
+  d.in_valid = in.take(n);
+  d.in_p1 = in.take(12 * n);
+  d.in_p2 = in.take(12 * n);
+  d.in_kp1 = in.take(8 * n);
+  d.in_kp2 = in.take(8 * n);
+  d.in_is1 = in.take(4 * n);
+  d.in_is2 = in.take(4 * n);
+  d.o_out = res.take(sizeof(OsOut));
+  d.o_mask = res.take(8 * ((n + 63) / 64));
+}
+
+// A handle's buffer sizes: the record table and S problems at the bound
+inline void os_plan_bounds(size_t S, size_t C, size_t* in_bytes, size_t* res_bytes) {
+  OrbfeStage in, res;
+  OsDev d;
+  in.take(sizeof(OsDev) * S);
+  for (size_t s = 0; s < S; s++) os_layout(in, res, C, d);
+  *in_bytes = in.off, *res_bytes = res.off;
+}

@@ -27,28 +27,15 @@
 #include "orbfe_ktimer.h"
 #include "orbfe_match_internal.h"
 #include "orbfe_pnp_core.h"
+#include "orbfe_stage.h"
 
 static_assert(PNP_FLAG_SVD_NULL == ORBFE_PNP_FLAG_SVD_NULL && PNP_FLAG_QR_SINGULAR == ORBFE_PNP_FLAG_QR_SINGULAR,
               "flag values");
+static_assert(PNP_R == ORBFE_PNP_MAX_RECORDS, "records per solver");
 
 #define PNP_HYP_PER_BLOCK 4
 #define PNP_INL_THREADS 256
 #define PNP_INL_WAVES (PNP_INL_THREADS / 64)
-#define PNP_R ORBFE_PNP_MAX_RECORDS
-#define PNP_WS_DOUBLES 12  // per correspondence of a record: pws 3, us 2, alphas 4, pcs 3
-
-// One launched solver, as the kernels see it. in_* are byte offsets into the upload buffer, o_* into
-// the result buffer, ws into the refinement workspace.
-struct PnpDev {
-  int n, n_eval, min_inliers, max_its, words, pad0, pad1, pad2;
-  double K[4];
-  unsigned long long in_p3d, in_p2d, in_max, in_rand;
-  unsigned long long o_mask, o_r, o_t, o_tcw, o_N, o_flags, o_cnt, o_slot;          // per hypothesis
-  unsigned long long o_rec, o_rmask, o_rr, o_rt, o_rtcw, o_rN, o_rflags, o_rcnt;  // per record
-  unsigned long long o_sel, ws;
-};
-// o_sel: accepted, accepted_inliers, best, best_inliers, no_more, n_records, overflow
-#define PNP_SEL_INTS 8
 
 template <int W>
 struct PnpDevGroup {
@@ -258,26 +245,13 @@ struct PnpLast {  // one solver of the last solve, for orbfe_pnp_iterate
   size_t o_mask = 0, o_tcw = 0, o_cnt = 0, o_slot = 0, o_rmask = 0, o_rtcw = 0, o_rcnt = 0;
 };
 
-struct orbfe_pnp {
-  int device = -1;
+struct orbfe_pnp : OrbfeDev {
   int S = 0, C = 0, H = 0;
-  hipStream_t stream = nullptr;
-  uint8_t *d_in = nullptr, *h_in = nullptr, *d_res = nullptr, *h_res = nullptr;
-  double* d_ws = nullptr;
-  size_t in_bytes = 0, res_bytes = 0, ws_bytes = 0;
+  // inputs (one upload), results (one copy back), the refinement workspace (device only); sized by
+  // pnp_plan_bounds
+  OrbfeStage in, res, ws;
   std::vector<PnpLast> last;
 };
-
-static size_t pnp_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t pnp_in_bytes(size_t n, size_t e) {
-  return pnp_al(12 * n) + pnp_al(8 * n) + pnp_al(4 * n) + pnp_al(16 * e);
-}
-static size_t pnp_res_bytes(size_t n, size_t e) {
-  const size_t w = (n + 63) / 64, r = PNP_R;
-  return pnp_al(8 * w * e) + pnp_al(72 * e) + pnp_al(24 * e) + pnp_al(48 * e) + 4 * pnp_al(4 * e) + pnp_al(4 * r) +
-         pnp_al(8 * w * r) + pnp_al(72 * r) + pnp_al(24 * r) + pnp_al(48 * r) + 3 * pnp_al(4 * r) +
-         pnp_al(4 * PNP_SEL_INTS);
-}
 
 struct PnpParams {
   int min_inliers, max_its;
@@ -294,14 +268,7 @@ static PnpParams pnp_ransac_params(int n, double probability, int min_inliers, i
   p.min_inliers = n_min;
   if (epsilon < (float)n_min / (float)n) epsilon = (float)n_min / (float)n;
   p.epsilon = epsilon;
-  int n_it;
-  if (n_min == n) {
-    n_it = 1;
-  } else {
-    const double q = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-    n_it = (q > -2147483649.0 && q < 2147483648.0) ? (int)q : INT_MIN;  // x86's out-of-range conversion
-  }
-  p.max_its = std::max(1, std::min(n_it, max_iterations));
+  p.max_its = ransac_max_its(n, n_min, epsilon, probability, max_iterations);
   return p;
 }
 
@@ -320,48 +287,26 @@ extern "C" int orbfe_pnp_create(int device, int max_solvers, int max_corr, int m
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_pnp_create: no such HIP device");
-  }
-  h->device = device;
-  h->in_bytes = pnp_al(sizeof(PnpDev) * (size_t)h->S) + (size_t)h->S * pnp_in_bytes(h->C, h->H);
-  h->res_bytes = (size_t)h->S * pnp_res_bytes(h->C, h->H);
-  h->ws_bytes = (size_t)h->S * PNP_R * PNP_WS_DOUBLES * 8 * (size_t)h->C;
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int st = orbfe_dev_open(h, device, "orbfe_pnp_create");
+  if (st != ORBFE_OK) {
     orbfe_pnp_destroy(h);
     return st;
-  };
-#define PNP_TRY(expr)                             \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  PNP_TRY(hipSetDevice(device));
-  PNP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PNP_TRY(hipMalloc(&h->d_in, h->in_bytes));
-  PNP_TRY(hipMalloc(&h->d_res, h->res_bytes));
-  PNP_TRY(hipMalloc(&h->d_ws, h->ws_bytes));
-  PNP_TRY(hipHostMalloc(&h->h_in, h->in_bytes, hipHostMallocDefault));
-  PNP_TRY(hipHostMalloc(&h->h_res, h->res_bytes, hipHostMallocDefault));
-#undef PNP_TRY
+  }
+  size_t in_bytes, res_bytes, ws_bytes;
+  pnp_plan_bounds(h->S, h->C, h->H, &in_bytes, &res_bytes, &ws_bytes);
+  ORBFE_CREATE_HIP(h, orbfe_pnp_destroy, orbfe_stage_alloc(&h->in, in_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_pnp_destroy, orbfe_stage_alloc(&h->res, res_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_pnp_destroy, orbfe_stage_alloc(&h->ws, ws_bytes, false));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_pnp_destroy(orbfe_pnp* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_in);
-    hipFree(h->d_res);
-    hipFree(h->d_ws);
-    if (h->h_in) hipHostFree(h->h_in);
-    if (h->h_res) hipHostFree(h->h_res);
-    if (h->stream) hipStreamDestroy(h->stream);
+  if (orbfe_dev_close(h)) {
+    orbfe_stage_free(&h->in);
+    orbfe_stage_free(&h->res);
+    orbfe_stage_free(&h->ws);
   }
   delete h;
   return ORBFE_OK;
@@ -402,13 +347,9 @@ static int pnp_check_solver(const orbfe_pnp* h, const orbfe_pnp_solver_t* s, con
     if (!(a >= 0.0f && a < 1e15f))
       return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_pnp_solve_batch: sigma2 must be finite and >= 0");
   }
-  for (int k = 0; k < e; k++)
-    for (int i = 0; i < 4; i++) {
-      const int d = s->rand_idx[4 * (size_t)k + i];
-      if (d < 0 || d > s->n - 1 - i)
-        return orbfe_set_error(ORBFE_ERR_ARG,
-                               "orbfe_pnp_solve_batch: rand_idx outside 0 .. n-1-i for draw i of its iteration");
-    }
+  if (!ransac_check_draws(s->rand_idx, e, 4, s->n))
+    return orbfe_set_error(ORBFE_ERR_ARG,
+                           "orbfe_pnp_solve_batch: rand_idx outside 0 .. n-1-i for draw i of its iteration");
   *n_eval = e;
   return ORBFE_OK;
 }
@@ -432,12 +373,14 @@ extern "C" int orbfe_pnp_solve_batch(orbfe_pnp* h, const orbfe_pnp_solver_t* sol
   for (int i = 0; i < n_solvers; i++)
     if (n_eval[i] > 0) act.push_back(i);
   const int na = (int)act.size();
-  PnpDev* dev = reinterpret_cast<PnpDev*>(h->h_in);
-  size_t in_off = pnp_al(sizeof(PnpDev) * (size_t)std::max(na, 1)), res_off = 0, ws_off = 0;
+  OrbfeStage &in = h->in, &res = h->res, &ws = h->ws;
+  in.off = res.off = ws.off = 0;
+  PnpDev* dev;
+  in.take<PnpDev>((size_t)std::max(na, 1), &dev);
   int max_e = 0;
   for (int a = 0; a < na; a++) {
     const orbfe_pnp_solver_t& s = solvers[act[a]];
-    const size_t n = (size_t)s.n, e = (size_t)n_eval[act[a]], r = PNP_R;
+    const size_t n = (size_t)s.n, e = (size_t)n_eval[act[a]];
     PnpDev d;
     memset(&d, 0, sizeof(d));
     d.n = s.n;
@@ -446,47 +389,14 @@ extern "C" int orbfe_pnp_solve_batch(orbfe_pnp* h, const orbfe_pnp_solver_t* sol
     d.max_its = prm[act[a]].max_its;
     d.words = (s.n + 63) / 64;
     for (int i = 0; i < 4; i++) d.K[i] = (double)s.k[i];  // fu = F.fx ... (:111-114): float widened to double
-    auto take_in = [&](size_t bytes) {
-      const size_t o = in_off;
-      in_off += pnp_al(bytes);
-      return o;
-    };
-    auto take_res = [&](size_t bytes) {
-      const size_t o = res_off;
-      res_off += pnp_al(bytes);
-      return o;
-    };
-    const size_t w = (size_t)d.words;
-    d.in_p3d = take_in(12 * n);
-    d.in_p2d = take_in(8 * n);
-    d.in_max = take_in(4 * n);
-    d.in_rand = take_in(16 * e);
-    d.o_mask = take_res(8 * w * e);
-    d.o_r = take_res(72 * e);
-    d.o_t = take_res(24 * e);
-    d.o_tcw = take_res(48 * e);
-    d.o_N = take_res(4 * e);
-    d.o_flags = take_res(4 * e);
-    d.o_cnt = take_res(4 * e);
-    d.o_slot = take_res(4 * e);
-    d.o_rec = take_res(4 * r);
-    d.o_rmask = take_res(8 * w * r);
-    d.o_rr = take_res(72 * r);
-    d.o_rt = take_res(24 * r);
-    d.o_rtcw = take_res(48 * r);
-    d.o_rN = take_res(4 * r);
-    d.o_rflags = take_res(4 * r);
-    d.o_rcnt = take_res(4 * r);
-    d.o_sel = take_res(4 * PNP_SEL_INTS);
-    d.ws = ws_off;
-    ws_off += r * PNP_WS_DOUBLES * 8 * n;
-    if (in_off > h->in_bytes || res_off > h->res_bytes || ws_off > h->ws_bytes)  // cannot happen within the bounds
+    pnp_layout(in, res, ws, n, e, d);
+    if (in.off > in.cap || res.off > res.cap || ws.off > ws.cap)  // cannot happen within the bounds
       return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_pnp_solve_batch: staging plan exceeds the handle's buffers");
-    memcpy(h->h_in + d.in_p3d, s.p3dw, 12 * n);
-    memcpy(h->h_in + d.in_p2d, s.p2d, 8 * n);
-    float* mx = reinterpret_cast<float*>(h->h_in + d.in_max);
+    memcpy(in.h + d.in_p3d, s.p3dw, 12 * n);
+    memcpy(in.h + d.in_p2d, s.p2d, 8 * n);
+    float* mx = reinterpret_cast<float*>(in.h + d.in_max);
     for (size_t i = 0; i < n; i++) mx[i] = s.sigma2[i] * s.th2;  // mvMaxError (:165-167), float
-    memcpy(h->h_in + d.in_rand, s.rand_idx, 16 * e);
+    memcpy(in.h + d.in_rand, s.rand_idx, 16 * e);
     dev[a] = d;
     max_e = std::max(max_e, (int)e);
     PnpLast& L = h->last[act[a]];
@@ -504,10 +414,11 @@ extern "C" int orbfe_pnp_solve_batch(orbfe_pnp* h, const orbfe_pnp_solver_t* sol
   }
   if (na > 0) {
     ORBFE_HIP_CHECK(hipSetDevice(h->device));
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->d_in, h->h_in, in_off, hipMemcpyHostToDevice, h->stream));
-    const uint8_t* din = h->d_in;
-    uint8_t* dres = h->d_res;
-    double* dws = h->d_ws;
+    int st;
+    if ((st = orbfe_stage_upload(&in, h->stream)) != ORBFE_OK) return st;
+    const uint8_t* din = in.d;
+    uint8_t* dres = res.d;
+    double* dws = reinterpret_cast<double*>(ws.d);
     ORBFE_LAUNCH("k_pnp_hypotheses", k_pnp_hypotheses,
                  dim3((max_e + PNP_HYP_PER_BLOCK - 1) / PNP_HYP_PER_BLOCK, na), dim3(64), 0, h->stream, din, dres);
     ORBFE_LAUNCH("k_pnp_inliers", k_pnp_inliers, dim3((max_e + PNP_INL_WAVES - 1) / PNP_INL_WAVES, na),
@@ -517,9 +428,7 @@ extern "C" int orbfe_pnp_solve_batch(orbfe_pnp* h, const orbfe_pnp_solver_t* sol
     ORBFE_LAUNCH("k_pnp_inliers", k_pnp_inliers, dim3((PNP_R + PNP_INL_WAVES - 1) / PNP_INL_WAVES, na),
                  dim3(PNP_INL_THREADS), 0, h->stream, din, dres, 1);
     ORBFE_LAUNCH("k_pnp_select", k_pnp_select, dim3(1), dim3(64), 0, h->stream, din, dres, na);
-    ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, res_off, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if ((st = orbfe_stage_download(&res, h->stream)) != ORBFE_OK) return st;
   }
   for (int i = 0; i < n_solvers; i++) {
     orbfe_pnp_result_t& r = results[i];
@@ -538,27 +447,20 @@ extern "C" int orbfe_pnp_solve_batch(orbfe_pnp* h, const orbfe_pnp_solver_t* sol
     const PnpDev& d = dev[a];
     orbfe_pnp_result_t& r = results[act[a]];
     const size_t e = (size_t)d.n_eval;
-    const uint8_t* base = h->h_res;
+    const uint8_t* base = res.h;
     const int32_t* sel = reinterpret_cast<const int32_t*>(base + d.o_sel);
     if (sel[6]) {
       h->last.clear();
       return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_pnp_solve_batch: more than ORBFE_PNP_MAX_RECORDS records");
     }
     const size_t nr = (size_t)sel[5];
-    auto masks = [&](uint64_t* out, size_t off, size_t count) {
-      for (size_t k = 0; k < count; k++) {
-        uint64_t* dst = out + k * (size_t)r.mask_words;
-        memcpy(dst, base + off + 8 * (size_t)d.words * k, 8 * (size_t)d.words);
-        for (int w = d.words; w < r.mask_words; w++) dst[w] = 0;
-      }
-    };
     if (r.n_inliers) memcpy(r.n_inliers, base + d.o_cnt, 4 * e);
     if (r.r) memcpy(r.r, base + d.o_r, 72 * e);
     if (r.t) memcpy(r.t, base + d.o_t, 24 * e);
     if (r.tcw) memcpy(r.tcw, base + d.o_tcw, 48 * e);
     if (r.n_chosen) memcpy(r.n_chosen, base + d.o_N, 4 * e);
     if (r.flags) memcpy(r.flags, base + d.o_flags, 4 * e);
-    if (r.inlier_mask) masks(r.inlier_mask, d.o_mask, e);
+    if (r.inlier_mask) orbfe_unpack_masks(r.inlier_mask, r.mask_words, base + d.o_mask, d.words, e);
     if (r.records) memcpy(r.records, base + d.o_rec, 4 * nr);
     if (r.refined_inliers) memcpy(r.refined_inliers, base + d.o_rcnt, 4 * nr);
     if (r.refined_r) memcpy(r.refined_r, base + d.o_rr, 72 * nr);
@@ -566,7 +468,7 @@ extern "C" int orbfe_pnp_solve_batch(orbfe_pnp* h, const orbfe_pnp_solver_t* sol
     if (r.refined_tcw) memcpy(r.refined_tcw, base + d.o_rtcw, 48 * nr);
     if (r.refined_n_chosen) memcpy(r.refined_n_chosen, base + d.o_rN, 4 * nr);
     if (r.refined_flags) memcpy(r.refined_flags, base + d.o_rflags, 4 * nr);
-    if (r.refined_mask) masks(r.refined_mask, d.o_rmask, nr);
+    if (r.refined_mask) orbfe_unpack_masks(r.refined_mask, r.mask_words, base + d.o_rmask, d.words, nr);
     r.n_records = (int)nr;
     r.accepted = sel[0];
     r.accepted_inliers = sel[1];
@@ -597,9 +499,9 @@ extern "C" int orbfe_pnp_iterate(orbfe_pnp* h, int solver_index, int n_iteration
     return ORBFE_OK;
   }
   if (state->best >= L.n_eval) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_pnp_iterate: state is not this solver's");
-  const int32_t* cnt = reinterpret_cast<const int32_t*>(h->h_res + L.o_cnt);
-  const int32_t* slot = reinterpret_cast<const int32_t*>(h->h_res + L.o_slot);
-  const int32_t* rcnt = reinterpret_cast<const int32_t*>(h->h_res + L.o_rcnt);
+  const int32_t* cnt = reinterpret_cast<const int32_t*>(h->res.h + L.o_cnt);
+  const int32_t* slot = reinterpret_cast<const int32_t*>(h->res.h + L.o_slot);
+  const int32_t* rcnt = reinterpret_cast<const int32_t*>(h->res.h + L.o_rcnt);
   int cur = 0;
   // :193 as written: with ||, a call below mRansacMaxIts runs on to it
   while ((state->iterations < L.max_its || cur < n_iterations) && state->iterations < L.n_eval) {
@@ -617,8 +519,8 @@ extern "C" int orbfe_pnp_iterate(orbfe_pnp* h, int solver_index, int n_iteration
         out->returned = 1;
         out->accepted = state->best;
         out->n_inliers = rcnt[s];
-        memcpy(out->tcw, h->h_res + L.o_rtcw + 48 * (size_t)s, 48);
-        if (out->inlier_mask) memcpy(out->inlier_mask, h->h_res + L.o_rmask + 8 * (size_t)L.words * s, 8 * (size_t)L.words);
+        memcpy(out->tcw, h->res.h + L.o_rtcw + 48 * (size_t)s, 48);
+        if (out->inlier_mask) memcpy(out->inlier_mask, h->res.h + L.o_rmask + 8 * (size_t)L.words * s, 8 * (size_t)L.words);
         return ORBFE_OK;
       }
     }
@@ -628,9 +530,9 @@ extern "C" int orbfe_pnp_iterate(orbfe_pnp* h, int solver_index, int n_iteration
     if (state->best_inliers >= L.min_inliers && state->best >= 0) {
       out->returned = 2;
       out->n_inliers = state->best_inliers;
-      memcpy(out->tcw, h->h_res + L.o_tcw + 48 * (size_t)state->best, 48);
+      memcpy(out->tcw, h->res.h + L.o_tcw + 48 * (size_t)state->best, 48);
       if (out->inlier_mask)
-        memcpy(out->inlier_mask, h->h_res + L.o_mask + 8 * (size_t)L.words * state->best, 8 * (size_t)L.words);
+        memcpy(out->inlier_mask, h->res.h + L.o_mask + 8 * (size_t)L.words * state->best, 8 * (size_t)L.words);
     }
   }
   return ORBFE_OK;

@@ -24,6 +24,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "orbfe_stage.h"
+
 #define PNP_FLAG_SVD_NULL 1u     /* == ORBFE_PNP_FLAG_SVD_NULL */
 #define PNP_FLAG_QR_SINGULAR 2u  /* == ORBFE_PNP_FLAG_QR_SINGULAR */
 
@@ -547,4 +549,63 @@ PNP_HD inline bool pnp_is_inlier(const double* R, const double* t, const double*
   const float distY = (float)(v - ve);
   const float error2 = distX * distX + distY * distY;
   return error2 < max_error;
+}
+
+// ------------------------------------------------------------------------------------------
+// staging (host)
+
+#define PNP_R 16           /* == ORBFE_PNP_MAX_RECORDS */
+#define PNP_WS_DOUBLES 12  // per correspondence of a record: pws 3, us 2, alphas 4, pcs 3
+
+// One launched solver, as the kernels see it. in_* are byte offsets into the upload buffer, o_* into
+// the result buffer, ws into the refinement workspace.
+struct PnpDev {
+  int n, n_eval, min_inliers, max_its, words, pad0, pad1, pad2;
+  double K[4];
+  unsigned long long in_p3d, in_p2d, in_max, in_rand;
+  unsigned long long o_mask, o_r, o_t, o_tcw, o_N, o_flags, o_cnt, o_slot;          // per hypothesis
+  unsigned long long o_rec, o_rmask, o_rr, o_rt, o_rtcw, o_rN, o_rflags, o_rcnt;  // per record
+  unsigned long long o_sel, ws;
+};
+// o_sel: accepted, accepted_inliers, best, best_inliers, no_more, n_records, overflow
+#define PNP_SEL_INTS 8
+
+// The arrays of one solver with n correspondences and e hypotheses, taken from the three blocks in the
+// order the buffers hold them; fills d's offsets only. The one statement of the buffer plan: over counting
+// blocks it sizes a handle (pnp_plan_bounds), over the real ones it places a solve. The workspace holds
+// doubles only and is packed without the alignment step.
+inline void pnp_layout(OrbfeStage& in, OrbfeStage& res, OrbfeStage& ws, size_t n, size_t e, PnpDev& d) {
+  const size_t w = (n + 63) / 64, r = PNP_R;
+  d.in_p3d = in.take(12 * n);
+  d.in_p2d = in.take(8 * n);
+  d.in_max = in.take(4 * n);
+  d.in_rand = in.take(16 * e);
+  d.o_mask = res.take(8 * w * e);
+  d.o_r = res.take(72 * e);
+  d.o_t = res.take(24 * e);
+  d.o_tcw = res.take(48 * e);
+  d.o_N = res.take(4 * e);
+  d.o_flags = res.take(4 * e);
+  d.o_cnt = res.take(4 * e);
+  d.o_slot = res.take(4 * e);
+  d.o_rec = res.take(4 * r);
+  d.o_rmask = res.take(8 * w * r);
+  d.o_rr = res.take(72 * r);
+  d.o_rt = res.take(24 * r);
+  d.o_rtcw = res.take(48 * r);
+  d.o_rN = res.take(4 * r);
+  d.o_rflags = res.take(4 * r);
+  d.o_rcnt = res.take(4 * r);
+  d.o_sel = res.take(4 * PNP_SEL_INTS);
+  d.ws = ws.off;
+  ws.off += r * PNP_WS_DOUBLES * 8 * n;
+}
+
+// A handle's buffer sizes: the record table and S solvers at the bounds
+inline void pnp_plan_bounds(size_t S, size_t C, size_t H, size_t* in_bytes, size_t* res_bytes, size_t* ws_bytes) {
+  OrbfeStage in, res, ws;
+  PnpDev d;
+  in.take(sizeof(PnpDev) * S);
+  for (size_t s = 0; s < S; s++) pnp_layout(in, res, ws, C, H, d);
+  *in_bytes = in.off, *res_bytes = res.off, *ws_bytes = ws.off;
 }

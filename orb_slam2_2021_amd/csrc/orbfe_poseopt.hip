@@ -21,6 +21,7 @@
 #include "orbfe_ktimer.h"
 #include "orbfe_lm_device.h"
 #include "orbfe_poseopt_core.h"
+#include "orbfe_stage.h"
 
 static_assert(LM_FLAG_LARGE_STEP == ORBFE_POSEOPT_FLAG_LARGE_STEP && LM_FLAG_NONFINITE == ORBFE_POSEOPT_FLAG_NONFINITE,
               "flag values");
@@ -29,15 +30,6 @@ static_assert(LM_STOP_ALL == ORBFE_POSEOPT_STOP_ALL && LM_STOP_TERMINATE == ORBF
               "stop codes");
 static_assert(ORBFE_POSEOPT_MAX_OBS <= PO_LANES * 64, "a lane's outlier flags are one 64-bit word");
 static_assert(sizeof(PoRound) == sizeof(orbfe_poseopt_round_t), "trace layout");
-
-// One problem as the kernel sees it. in_* are byte offsets into the upload buffer, o_* into the result
-// buffer.
-struct PoDev {
-  int n, pad;
-  double cam[5];  // fx, fy, cx, cy, bf: float widened to double
-  float tcw[12];
-  unsigned long long in_valid, in_xw, in_kp, in_ur, in_is2, o_out, o_mask;
-};
 
 __global__ __launch_bounds__(PO_LANES) void k_poseopt(const uint8_t* __restrict__ in, uint8_t* __restrict__ res) {
   const PoDev& D = reinterpret_cast<const PoDev*>(in)[blockIdx.x];
@@ -68,17 +60,10 @@ __global__ __launch_bounds__(PO_LANES) void k_poseopt(const uint8_t* __restrict_
 // ------------------------------------------------------------------------------------------
 // host
 
-struct orbfe_poseopt {
-  int device = -1;
+struct orbfe_poseopt : OrbfeDev {
   int S = 0, C = 0;
-  hipStream_t stream = nullptr;
-  uint8_t *d_in = nullptr, *h_in = nullptr, *d_res = nullptr, *h_res = nullptr;
-  size_t in_bytes = 0, res_bytes = 0;
+  OrbfeStage in, res;  // inputs (one upload), results (one copy back); sized by po_plan_bounds
 };
-
-static size_t po_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t po_in_bytes(size_t n) { return po_al(n) + po_al(12 * n) + po_al(8 * n) + 2 * po_al(4 * n); }
-static size_t po_res_bytes(size_t n) { return po_al(sizeof(PoOut)) + po_al(8 * ((n + 63) / 64)); }
 
 extern "C" int orbfe_poseopt_create(int device, int max_problems, int max_obs, orbfe_poseopt** out) {
   if (!out) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_poseopt_create: bad argument");
@@ -92,45 +77,24 @@ extern "C" int orbfe_poseopt_create(int device, int max_problems, int max_obs, o
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_poseopt_create: no such HIP device");
-  }
-  h->device = device;
-  h->in_bytes = po_al(sizeof(PoDev) * (size_t)h->S) + (size_t)h->S * po_in_bytes(h->C);
-  h->res_bytes = (size_t)h->S * po_res_bytes(h->C);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int st = orbfe_dev_open(h, device, "orbfe_poseopt_create");
+  if (st != ORBFE_OK) {
     orbfe_poseopt_destroy(h);
     return st;
-  };
-#define PO_TRY(expr)                              \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  PO_TRY(hipSetDevice(device));
-  PO_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  PO_TRY(hipMalloc(&h->d_in, h->in_bytes));
-  PO_TRY(hipMalloc(&h->d_res, h->res_bytes));
-  PO_TRY(hipHostMalloc(&h->h_in, h->in_bytes, hipHostMallocDefault));
-  PO_TRY(hipHostMalloc(&h->h_res, h->res_bytes, hipHostMallocDefault));
-#undef PO_TRY
+  }
+  size_t in_bytes, res_bytes;
+  po_plan_bounds(h->S, h->C, &in_bytes, &res_bytes);
+  ORBFE_CREATE_HIP(h, orbfe_poseopt_destroy, orbfe_stage_alloc(&h->in, in_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_poseopt_destroy, orbfe_stage_alloc(&h->res, res_bytes, true));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_poseopt_destroy(orbfe_poseopt* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_in);
-    hipFree(h->d_res);
-    if (h->h_in) hipHostFree(h->h_in);
-    if (h->h_res) hipHostFree(h->h_res);
-    if (h->stream) hipStreamDestroy(h->stream);
+  if (orbfe_dev_close(h)) {
+    orbfe_stage_free(&h->in);
+    orbfe_stage_free(&h->res);
   }
   delete h;
   return ORBFE_OK;
@@ -157,8 +121,10 @@ extern "C" int orbfe_poseopt_batch(orbfe_poseopt* h, const orbfe_poseopt_problem
     if (st != ORBFE_OK) return st;
   }
   if (h->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "pose optimizer is host-only (device < 0)");
-  PoDev* dev = reinterpret_cast<PoDev*>(h->h_in);
-  size_t in_off = po_al(sizeof(PoDev) * (size_t)n_problems), res_off = 0;
+  OrbfeStage &in = h->in, &res = h->res;
+  in.off = res.off = 0;
+  PoDev* dev;
+  in.take<PoDev>((size_t)n_problems, &dev);
   for (int i = 0; i < n_problems; i++) {
     const orbfe_poseopt_problem_t& p = problems[i];
     const size_t n = (size_t)p.n;
@@ -168,43 +134,29 @@ extern "C" int orbfe_poseopt_batch(orbfe_poseopt* h, const orbfe_poseopt_problem
     for (int k = 0; k < 4; k++) d.cam[k] = (double)p.k[k];  // e->fx = pFrame->fx ...: float widened to double
     d.cam[4] = (double)p.bf;
     memcpy(d.tcw, p.tcw, sizeof(d.tcw));
-    auto take_in = [&](size_t bytes) {
-      const size_t o = in_off;
-      in_off += po_al(bytes);
-      return o;
-    };
-    d.in_valid = take_in(n);
-    d.in_xw = take_in(12 * n);
-    d.in_kp = take_in(8 * n);
-    d.in_ur = take_in(4 * n);
-    d.in_is2 = take_in(4 * n);
-    d.o_out = res_off;
-    res_off += po_al(sizeof(PoOut));
-    d.o_mask = res_off;
-    res_off += po_al(8 * ((n + 63) / 64));
-    if (in_off > h->in_bytes || res_off > h->res_bytes)  // cannot happen within the bounds
+    po_layout(in, res, n, d);
+    if (in.off > in.cap || res.off > res.cap)  // cannot happen within the bounds
       return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_poseopt_batch: staging plan exceeds the handle's buffers");
     if (n > 0) {
-      memcpy(h->h_in + d.in_valid, p.valid, n);
-      memcpy(h->h_in + d.in_xw, p.xw, 12 * n);
-      memcpy(h->h_in + d.in_kp, p.kp_un, 8 * n);
-      memcpy(h->h_in + d.in_ur, p.u_right, 4 * n);
-      memcpy(h->h_in + d.in_is2, p.inv_sigma2, 4 * n);
+      memcpy(in.h + d.in_valid, p.valid, n);
+      memcpy(in.h + d.in_xw, p.xw, 12 * n);
+      memcpy(in.h + d.in_kp, p.kp_un, 8 * n);
+      memcpy(in.h + d.in_ur, p.u_right, 4 * n);
+      memcpy(in.h + d.in_is2, p.inv_sigma2, 4 * n);
     }
     dev[i] = d;
   }
   ORBFE_HIP_CHECK(hipSetDevice(h->device));
-  ORBFE_HIP_CHECK(hipMemcpyAsync(h->d_in, h->h_in, in_off, hipMemcpyHostToDevice, h->stream));
-  const uint8_t* din = h->d_in;
-  uint8_t* dres = h->d_res;
+  int st;
+  if ((st = orbfe_stage_upload(&in, h->stream)) != ORBFE_OK) return st;
+  const uint8_t* din = in.d;
+  uint8_t* dres = res.d;
   ORBFE_LAUNCH("k_poseopt", k_poseopt, dim3(n_problems), dim3(PO_LANES), 0, h->stream, din, dres);
-  ORBFE_HIP_CHECK(hipGetLastError());
-  ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, res_off, hipMemcpyDeviceToHost, h->stream));
-  ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+  if ((st = orbfe_stage_download(&res, h->stream)) != ORBFE_OK) return st;
   for (int i = 0; i < n_problems; i++) {
     const PoDev& d = dev[i];
     orbfe_poseopt_result_t& r = results[i];
-    const PoOut* o = reinterpret_cast<const PoOut*>(h->h_res + d.o_out);
+    const PoOut* o = reinterpret_cast<const PoOut*>(res.h + d.o_out);
     memcpy(r.tcw, o->tcw, sizeof(r.tcw));
     memcpy(r.pose_q_t, o->pose, sizeof(r.pose_q_t));
     r.n_initial = o->n_initial;
@@ -213,11 +165,7 @@ extern "C" int orbfe_poseopt_batch(orbfe_poseopt* h, const orbfe_poseopt_problem
     r.rounds_run = o->rounds_run;
     r.flags = o->flags;
     memcpy(r.rounds, o->rounds, sizeof(r.rounds));
-    if (r.outlier_mask) {
-      const int words = (d.n + 63) / 64;
-      memcpy(r.outlier_mask, h->h_res + d.o_mask, 8 * (size_t)words);
-      for (int w = words; w < r.mask_words; w++) r.outlier_mask[w] = 0;
-    }
+    if (r.outlier_mask) orbfe_unpack_masks(r.outlier_mask, r.mask_words, res.h + d.o_mask, (d.n + 63) / 64, 1);
   }
   return ORBFE_OK;
 }

@@ -19,6 +19,7 @@
 // ceil(n / 64) edges per lane) and no computed value forms an address.
 #pragma once
 #include "orbfe_lm_core.h"
+#include "orbfe_stage.h"
 
 #define PO_ACC 28  // 21 lower entries of H (row-major over r >= c), 6 of b, the robust chi2
 
@@ -542,4 +543,38 @@ PO_HD inline void po_optimize(const G& g, const PoProblem& P, PoWork& w, PoOut* 
     o->flags = flags;
     o->pad = 0;
   }
+}
+
+// ------------------------------------------------------------------------------------------
+// staging (host)
+
+// One problem as the kernel sees it. in_* are byte offsets into the upload buffer, o_* into the result
+// buffer.
+struct PoDev {
+  int n, pad;
+  double cam[5];  // fx, fy, cx, cy, bf: float widened to double
+  float tcw[12];
+  unsigned long long in_valid, in_xw, in_kp, in_ur, in_is2, o_out, o_mask;
+};
+
+// The arrays of one problem with n observations, taken from the two blocks in the order the buffers hold
+// them; fills d's offsets only. The one statement of the buffer plan: over counting blocks it sizes a
+// handle (po_plan_bounds), over the real ones it places a batch.
+inline void po_layout(OrbfeStage& in, OrbfeStage& res, size_t n, PoDev& d) {
+  d.in_valid = in.take(n);
+  d.in_xw = in.take(12 * n);
+  d.in_kp = in.take(8 * n);
+  d.in_ur = in.take(4 * n);
+  d.in_is2 = in.take(4 * n);
+  d.o_out = res.take(sizeof(PoOut));
+  d.o_mask = res.take(8 * ((n + 63) / 64));
+}
+
+// A handle's buffer sizes: the record table and S problems at the bound
+inline void po_plan_bounds(size_t S, size_t C, size_t* in_bytes, size_t* res_bytes) {
+  OrbfeStage in, res;
+  PoDev d;
+  in.take(sizeof(PoDev) * S);
+  for (size_t s = 0; s < S; s++) po_layout(in, res, C, d);
+  *in_bytes = in.off, *res_bytes = res.off;
 }

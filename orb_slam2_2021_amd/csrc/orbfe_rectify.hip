@@ -16,6 +16,7 @@
 #include "orbfe_internal.h"
 #include "orbfe_ktimer.h"
 #include "orbfe_rectify_core.h"
+#include "orbfe_stage.h"
 
 struct orbfe_rectify_plan {
   int device = 0;
@@ -288,7 +289,7 @@ extern "C" int orbfe_rectified_stereo_frame(orbfe_extractor* h, const orbfe_rect
   const size_t row_bytes = (size_t)cols * channels;
   const bool side_by_side = right == left + row_bytes && step >= 2 * row_bytes;
   const size_t one = (size_t)(rows - 1) * step + row_bytes;
-  const size_t right_off = side_by_side ? row_bytes : ((one + 255) & ~(size_t)255);
+  const size_t right_off = side_by_side ? row_bytes : orbfe_al256(one);
   int st = grow(&S->d_src, &S->src_n, right_off + one);
   if (st != ORBFE_OK) return st;
   if ((st = grow(&S->d_planes, &S->planes_n, 2 * gpitch * out_rows)) != ORBFE_OK) return st;

@@ -22,19 +22,11 @@
 #include "orbfe_ktimer.h"
 #include "orbfe_match_internal.h"
 #include "orbfe_sim3_core.h"
+#include "orbfe_stage.h"
 
 #define SIM3_HYP_THREADS 64
 #define SIM3_INL_THREADS 256
 #define SIM3_INL_WAVES (SIM3_INL_THREADS / 64)
-
-// One launched solver, as the kernels see it. in_* are byte offsets into the upload buffer, o_* into
-// the result buffer.
-struct Sim3Dev {
-  int n, n_eval, fix_scale, min_inliers, max_its, has_hyp, words, pad;
-  float k1[4], k2[4];
-  unsigned long long in_x1, in_x2, in_max1, in_max2, in_rand, in_t12, in_t21;
-  unsigned long long o_mask, o_t12, o_t21, o_r, o_t, o_s, o_cnt, o_sel;
-};
 
 __global__ __launch_bounds__(SIM3_HYP_THREADS) void k_sim3_hypotheses(const uint8_t* __restrict__ in,
                                                                       uint8_t* __restrict__ res) {
@@ -173,36 +165,11 @@ struct Sim3Last {  // one solver of the last solve, for orbfe_sim3_iterate
   size_t o_mask = 0, o_t12 = 0, o_cnt = 0;
 };
 
-struct orbfe_sim3 {
-  int device = -1;
+struct orbfe_sim3 : OrbfeDev {
   int S = 0, C = 0, H = 0;
-  hipStream_t stream = nullptr;
-  uint8_t *d_in = nullptr, *h_in = nullptr, *d_res = nullptr, *h_res = nullptr;
-  size_t in_bytes = 0, res_bytes = 0;
+  OrbfeStage in, res;  // inputs (one upload), results (one copy back); sized by sim3_plan_bounds
   std::vector<Sim3Last> last;
 };
-
-static size_t sim3_al(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t sim3_in_bytes(size_t n, size_t e) {
-  return 2 * sim3_al(12 * n) + 2 * sim3_al(4 * n) + std::max(sim3_al(12 * e), 2 * sim3_al(48 * e));
-}
-static size_t sim3_res_bytes(size_t n, size_t e) {
-  const size_t w = (n + 63) / 64;
-  return sim3_al(8 * w * e) + 2 * sim3_al(48 * e) + sim3_al(36 * e) + sim3_al(12 * e) + 2 * sim3_al(4 * e) + 256;
-}
-
-// mRansacMaxIts (:124-134)
-static int sim3_max_its(int n, int min_inliers, int max_iterations, double probability) {
-  const float epsilon = (float)min_inliers / n;
-  int n_it;
-  if (min_inliers == n) {
-    n_it = 1;
-  } else {
-    const double q = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-    n_it = (q > -2147483649.0 && q < 2147483648.0) ? (int)q : INT_MIN;  // x86's out-of-range conversion
-  }
-  return std::max(1, std::min(n_it, max_iterations));
-}
 
 extern "C" int orbfe_sim3_create(int device, int max_solvers, int max_corr, int max_hyp, orbfe_sim3** out) {
   if (!out) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_sim3_create: bad argument");
@@ -219,45 +186,24 @@ extern "C" int orbfe_sim3_create(int device, int max_solvers, int max_corr, int 
     *out = h;
     return ORBFE_OK;
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) {
-    delete h;
-    return orbfe_set_error(ORBFE_ERR_HIP, "orbfe_sim3_create: no such HIP device");
-  }
-  h->device = device;
-  h->in_bytes = sim3_al(sizeof(Sim3Dev) * (size_t)h->S) + (size_t)h->S * sim3_in_bytes(h->C, h->H);
-  h->res_bytes = (size_t)h->S * sim3_res_bytes(h->C, h->H);
-  auto fail = [&](hipError_t e, const char* what) {
-    const int st = orbfe_set_hip_error(e, what);
+  const int st = orbfe_dev_open(h, device, "orbfe_sim3_create");
+  if (st != ORBFE_OK) {
     orbfe_sim3_destroy(h);
     return st;
-  };
-#define SIM3_TRY(expr)                            \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return fail(_e, #expr); \
-  } while (0)
-  SIM3_TRY(hipSetDevice(device));
-  SIM3_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  SIM3_TRY(hipMalloc(&h->d_in, h->in_bytes));
-  SIM3_TRY(hipMalloc(&h->d_res, h->res_bytes));
-  SIM3_TRY(hipHostMalloc(&h->h_in, h->in_bytes, hipHostMallocDefault));
-  SIM3_TRY(hipHostMalloc(&h->h_res, h->res_bytes, hipHostMallocDefault));
-#undef SIM3_TRY
+  }
+  size_t in_bytes, res_bytes;
+  sim3_plan_bounds(h->S, h->C, h->H, &in_bytes, &res_bytes);
+  ORBFE_CREATE_HIP(h, orbfe_sim3_destroy, orbfe_stage_alloc(&h->in, in_bytes, true));
+  ORBFE_CREATE_HIP(h, orbfe_sim3_destroy, orbfe_stage_alloc(&h->res, res_bytes, true));
   *out = h;
   return ORBFE_OK;
 }
 
 extern "C" int orbfe_sim3_destroy(orbfe_sim3* h) {
   if (!h) return ORBFE_OK;
-  if (h->device >= 0) {
-    hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    hipFree(h->d_in);
-    hipFree(h->d_res);
-    if (h->h_in) hipHostFree(h->h_in);
-    if (h->h_res) hipHostFree(h->h_res);
-    if (h->stream) hipStreamDestroy(h->stream);
+  if (orbfe_dev_close(h)) {
+    orbfe_stage_free(&h->in);
+    orbfe_stage_free(&h->res);
   }
   delete h;
   return ORBFE_OK;
@@ -283,7 +229,8 @@ static int sim3_check_solver(const orbfe_sim3* h, const orbfe_sim3_solver_t* s, 
     return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_sim3_solve_batch: hyp_t12 and hyp_t21 go together");
   if (!has_hyp && s->n_hyp > 0 && !s->rand_idx)
     return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_sim3_solve_batch: null rand_idx");
-  *max_its = sim3_max_its(s->n, s->min_inliers, s->max_iterations, s->probability);
+  // mRansacMaxIts (:124-134): epsilon = (float)mRansacMinInliers / N
+  *max_its = ransac_max_its(s->n, s->min_inliers, (float)s->min_inliers / s->n, s->probability, s->max_iterations);
   const int e = std::min(s->n_hyp, *max_its);
   if (e > h->H)
     return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_sim3_solve_batch: more hypotheses than the handle's max_hyp");
@@ -294,14 +241,9 @@ static int sim3_check_solver(const orbfe_sim3* h, const orbfe_sim3_solver_t* s, 
     if (!(a >= 0.0f && a < 1e15f && b >= 0.0f && b < 1e15f))
       return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_sim3_solve_batch: sigma2 must be finite and >= 0");
   }
-  if (!has_hyp)
-    for (int k = 0; k < e; k++)
-      for (int i = 0; i < 3; i++) {
-        const int d = s->rand_idx[3 * (size_t)k + i];
-        if (d < 0 || d > s->n - 1 - i)
-          return orbfe_set_error(ORBFE_ERR_ARG,
-                                 "orbfe_sim3_solve_batch: rand_idx outside 0 .. n-1-i for draw i of its iteration");
-      }
+  if (!has_hyp && !ransac_check_draws(s->rand_idx, e, 3, s->n))
+    return orbfe_set_error(ORBFE_ERR_ARG,
+                           "orbfe_sim3_solve_batch: rand_idx outside 0 .. n-1-i for draw i of its iteration");
   *n_eval = e;
   return ORBFE_OK;
 }
@@ -324,8 +266,10 @@ extern "C" int orbfe_sim3_solve_batch(orbfe_sim3* h, const orbfe_sim3_solver_t* 
   for (int i = 0; i < n_solvers; i++)
     if (n_eval[i] > 0) act.push_back(i);
   const int na = (int)act.size();
-  Sim3Dev* dev = reinterpret_cast<Sim3Dev*>(h->h_in);
-  size_t in_off = sim3_al(sizeof(Sim3Dev) * (size_t)std::max(na, 1)), res_off = 0;
+  OrbfeStage &in = h->in, &res = h->res;
+  in.off = res.off = 0;
+  Sim3Dev* dev;
+  in.take<Sim3Dev>((size_t)std::max(na, 1), &dev);
   int max_e = 0;
   for (int a = 0; a < na; a++) {
     const orbfe_sim3_solver_t& s = solvers[act[a]];
@@ -341,50 +285,23 @@ extern "C" int orbfe_sim3_solve_batch(orbfe_sim3* h, const orbfe_sim3_solver_t* 
     d.words = (s.n + 63) / 64;
     memcpy(d.k1, s.k1, sizeof(d.k1));
     memcpy(d.k2, s.k2, sizeof(d.k2));
-    auto take_in = [&](size_t bytes) {
-      const size_t o = in_off;
-      in_off += sim3_al(bytes);
-      return o;
-    };
-    auto take_res = [&](size_t bytes) {
-      const size_t o = res_off;
-      res_off += sim3_al(bytes);
-      return o;
-    };
-    d.in_x1 = take_in(12 * n);
-    d.in_x2 = take_in(12 * n);
-    d.in_max1 = take_in(4 * n);
-    d.in_max2 = take_in(4 * n);
-    if (d.has_hyp) {
-      d.in_t12 = take_in(48 * e);
-      d.in_t21 = take_in(48 * e);
-    } else {
-      d.in_rand = take_in(12 * e);
-    }
-    d.o_mask = take_res(8 * (size_t)d.words * e);
-    d.o_t12 = take_res(48 * e);
-    d.o_t21 = take_res(48 * e);
-    d.o_r = take_res(36 * e);
-    d.o_t = take_res(12 * e);
-    d.o_s = take_res(4 * e);
-    d.o_cnt = take_res(4 * e);
-    d.o_sel = take_res(32);
-    if (in_off > h->in_bytes || res_off > h->res_bytes)  // cannot happen within the handle's bounds
+    sim3_layout(in, res, n, e, d.has_hyp != 0, d);
+    if (in.off > in.cap || res.off > res.cap)  // cannot happen within the handle's bounds
       return orbfe_set_error(ORBFE_ERR_CAPACITY, "orbfe_sim3_solve_batch: staging plan exceeds the handle's buffers");
-    memcpy(h->h_in + d.in_x1, s.x3dc1, 12 * n);
-    memcpy(h->h_in + d.in_x2, s.x3dc2, 12 * n);
-    float* m1 = reinterpret_cast<float*>(h->h_in + d.in_max1);
-    float* m2 = reinterpret_cast<float*>(h->h_in + d.in_max2);
+    memcpy(in.h + d.in_x1, s.x3dc1, 12 * n);
+    memcpy(in.h + d.in_x2, s.x3dc2, 12 * n);
+    float* m1 = reinterpret_cast<float*>(in.h + d.in_max1);
+    float* m2 = reinterpret_cast<float*>(in.h + d.in_max2);
     for (size_t i = 0; i < n; i++) {
       // mvnMaxError is std::vector<size_t>: truncated; the comparison converts it to float
       m1[i] = (float)(size_t)(9.210 * (double)s.sigma2_1[i]);
       m2[i] = (float)(size_t)(9.210 * (double)s.sigma2_2[i]);
     }
     if (d.has_hyp) {
-      memcpy(h->h_in + d.in_t12, s.hyp_t12, 48 * e);
-      memcpy(h->h_in + d.in_t21, s.hyp_t21, 48 * e);
+      memcpy(in.h + d.in_t12, s.hyp_t12, 48 * e);
+      memcpy(in.h + d.in_t21, s.hyp_t21, 48 * e);
     } else {
-      memcpy(h->h_in + d.in_rand, s.rand_idx, 12 * e);
+      memcpy(in.h + d.in_rand, s.rand_idx, 12 * e);
     }
     dev[a] = d;
     max_e = std::max(max_e, (int)e);
@@ -404,18 +321,17 @@ extern "C" int orbfe_sim3_solve_batch(orbfe_sim3* h, const orbfe_sim3_solver_t* 
   }
   if (na > 0) {
     ORBFE_HIP_CHECK(hipSetDevice(h->device));
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->d_in, h->h_in, in_off, hipMemcpyHostToDevice, h->stream));
-    const uint8_t* din = h->d_in;
-    uint8_t* dres = h->d_res;
+    int st;
+    if ((st = orbfe_stage_upload(&in, h->stream)) != ORBFE_OK) return st;
+    const uint8_t* din = in.d;
+    uint8_t* dres = res.d;
     ORBFE_LAUNCH("k_sim3_hypotheses", k_sim3_hypotheses,
                  dim3((max_e + SIM3_HYP_THREADS - 1) / SIM3_HYP_THREADS, na), dim3(SIM3_HYP_THREADS), 0, h->stream, din,
                  dres);
     ORBFE_LAUNCH("k_sim3_inliers", k_sim3_inliers, dim3((max_e + SIM3_INL_WAVES - 1) / SIM3_INL_WAVES, na),
                  dim3(SIM3_INL_THREADS), 0, h->stream, din, dres);
     ORBFE_LAUNCH("k_sim3_select", k_sim3_select, dim3(1), dim3(64), 0, h->stream, din, dres, na);
-    ORBFE_HIP_CHECK(hipGetLastError());
-    ORBFE_HIP_CHECK(hipMemcpyAsync(h->h_res, h->d_res, res_off, hipMemcpyDeviceToHost, h->stream));
-    ORBFE_HIP_CHECK(hipStreamSynchronize(h->stream));
+    if ((st = orbfe_stage_download(&res, h->stream)) != ORBFE_OK) return st;
   }
   for (int i = 0; i < n_solvers; i++) {
     orbfe_sim3_result_t& r = results[i];
@@ -431,19 +347,14 @@ extern "C" int orbfe_sim3_solve_batch(orbfe_sim3* h, const orbfe_sim3_solver_t* 
     const Sim3Dev& d = dev[a];
     orbfe_sim3_result_t& r = results[act[a]];
     const size_t e = (size_t)d.n_eval;
-    const uint8_t* base = h->h_res;
+    const uint8_t* base = res.h;
     if (r.n_inliers) memcpy(r.n_inliers, base + d.o_cnt, 4 * e);
     if (r.t12) memcpy(r.t12, base + d.o_t12, 48 * e);
     if (r.t21) memcpy(r.t21, base + d.o_t21, 48 * e);
     if (r.r12) memcpy(r.r12, base + d.o_r, 36 * e);
     if (r.tr12) memcpy(r.tr12, base + d.o_t, 12 * e);
     if (r.s12) memcpy(r.s12, base + d.o_s, 4 * e);
-    if (r.inlier_mask)
-      for (size_t k = 0; k < e; k++) {
-        uint64_t* dst = r.inlier_mask + k * (size_t)r.mask_words;
-        memcpy(dst, base + d.o_mask + 8 * (size_t)d.words * k, 8 * (size_t)d.words);
-        for (int w = d.words; w < r.mask_words; w++) dst[w] = 0;
-      }
+    if (r.inlier_mask) orbfe_unpack_masks(r.inlier_mask, r.mask_words, base + d.o_mask, d.words, e);
     const int32_t* sel = reinterpret_cast<const int32_t*>(base + d.o_sel);
     r.accepted = sel[0];
     r.accepted_inliers = sel[1];
@@ -473,7 +384,7 @@ extern "C" int orbfe_sim3_iterate(orbfe_sim3* h, int solver_index, int n_iterati
     return ORBFE_OK;
   }
   if (state->best >= L.n_eval) return orbfe_set_error(ORBFE_ERR_ARG, "orbfe_sim3_iterate: state is not this solver's");
-  const int32_t* cnt = reinterpret_cast<const int32_t*>(h->h_res + L.o_cnt);
+  const int32_t* cnt = reinterpret_cast<const int32_t*>(h->res.h + L.o_cnt);
   int cur = 0;
   while (state->iterations < L.max_its && cur < n_iterations && state->iterations < L.n_eval) {
     cur++;
@@ -484,8 +395,8 @@ extern "C" int orbfe_sim3_iterate(orbfe_sim3* h, int solver_index, int n_iterati
       if (cnt[k] > L.min_inliers) {
         out->accepted = k;
         out->n_inliers = cnt[k];
-        memcpy(out->t12, h->h_res + L.o_t12 + 48 * (size_t)k, 48);
-        if (out->inlier_mask) memcpy(out->inlier_mask, h->h_res + L.o_mask + 8 * (size_t)L.words * k, 8 * (size_t)L.words);
+        memcpy(out->t12, h->res.h + L.o_t12 + 48 * (size_t)k, 48);
+        if (out->inlier_mask) memcpy(out->inlier_mask, h->res.h + L.o_mask + 8 * (size_t)L.words * k, 8 * (size_t)L.words);
         return ORBFE_OK;
       }
     }

@@ -10,6 +10,8 @@
 #include <cfloat>
 #include <cmath>
 
+#include "orbfe_stage.h"
+
 #define SIM3_JACOBI_MAX_ROTATIONS (4 * 4 * 30)
 
 // The three correspondences of one iteration: swap-remove on a fresh 0..n-1 list (:162-176), kept
@@ -228,4 +230,55 @@ __host__ __device__ inline void sim3_compute(const float P1[3][3], const float P
     T21[4 * i + 3] = (float)(-1.0 * v);
   }
   *s_out = s;
+}
+
+// ------------------------------------------------------------------------------------------
+// staging (host)
+
+// One launched solver, as the kernels see it. in_* are byte offsets into the upload buffer, o_* into
+// the result buffer.
+struct Sim3Dev {
+  int n, n_eval, fix_scale, min_inliers, max_its, has_hyp, words, pad;
+  float k1[4], k2[4];
+  unsigned long long in_x1, in_x2, in_max1, in_max2, in_rand, in_t12, in_t21;
+  unsigned long long o_mask, o_t12, o_t21, o_r, o_t, o_s, o_cnt, o_sel;
+};
+
+// The arrays of one solver with n correspondences and e evaluated hypotheses, taken from the two blocks
+// in the order the buffers hold them; fills d's offsets only. The one statement of the buffer plan: over
+// counting blocks it sizes a handle (sim3_plan_bounds), over the real ones it places a solve.
+inline void sim3_layout(OrbfeStage& in, OrbfeStage& res, size_t n, size_t e, bool has_hyp, Sim3Dev& d) {
+  const size_t w = (n + 63) / 64;
+  d.in_x1 = in.take(12 * n);
+  d.in_x2 = in.take(12 * n);
+  d.in_max1 = in.take(4 * n);
+  d.in_max2 = in.take(4 * n);
+  if (has_hyp) {
+    d.in_t12 = in.take(48 * e);
+    d.in_t21 = in.take(48 * e);
+  } else {
+    d.in_rand = in.take(12 * e);
+  }
+  d.o_mask = res.take(8 * w * e);
+  d.o_t12 = res.take(48 * e);
+  d.o_t21 = res.take(48 * e);
+  d.o_r = res.take(36 * e);
+  d.o_t = res.take(12 * e);
+  d.o_s = res.take(4 * e);
+  d.o_cnt = res.take(4 * e);
+  d.o_sel = res.take(32);
+}
+
+// A handle's buffer sizes: the record table and S solvers at the bounds, in the larger of the two
+// hypothesis modes
+inline void sim3_plan_bounds(size_t S, size_t C, size_t H, size_t* in_bytes, size_t* res_bytes) {
+  *in_bytes = *res_bytes = 0;
+  for (int has_hyp = 0; has_hyp < 2; has_hyp++) {
+    OrbfeStage in, res;
+    Sim3Dev d;
+    in.take(sizeof(Sim3Dev) * S);
+    for (size_t s = 0; s < S; s++) sim3_layout(in, res, C, H, has_hyp != 0, d);
+    *in_bytes = std::max(*in_bytes, in.off);
+    *res_bytes = std::max(*res_bytes, res.off);
+  }
 }

@@ -342,7 +342,7 @@ extern "C" int orbfe_create_new_mappoints_device(orbfe_matcher* m, const orbfe_f
   ORBFE_HIP_CHECK(hipSetDevice(m->device));
   hipStream_t s = stream ? (hipStream_t)stream : m->stream;
   // one upload of every neighbour's two records, then three launches per neighbour
-  const size_t tri_bytes = (sizeof(orbfe_tri_pair) * (size_t)n_nb + 255) & ~(size_t)255;
+  const size_t tri_bytes = orbfe_al256(sizeof(orbfe_tri_pair) * (size_t)n_nb);
   const size_t bytes = tri_bytes + sizeof(orbfe_sft_pair) * (size_t)n_nb;
   const int st = tri_reserve(m, bytes);
   if (st) return st;

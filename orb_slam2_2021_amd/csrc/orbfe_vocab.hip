@@ -41,6 +41,7 @@
 #include "../../include/orbfe_vocab.h"
 #include "orbfe_device.h"
 #include "orbfe_ktimer.h"
+#include "orbfe_stage.h"
 
 #define VOCAB_MAX_FEATURES 8192
 #define VOCAB_MAX_CHILDREN (1 << 23)  // sibling index field of the min key
@@ -796,8 +797,7 @@ extern "C" int orbfe_vocab_transform(orbfe_vocabulary* v, const uint8_t* desc, i
   if (n > VOCAB_MAX_FEATURES) return orbfe_set_error(ORBFE_ERR_ARG, "too many descriptors");
   if (v->device < 0) return orbfe_set_error(ORBFE_ERR_STATE, "vocabulary loaded host-only (device < 0)");
   hipSetDevice(v->device);
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_desc = al((size_t)n * 32), b_i = al((size_t)n * 4 + 4), b_d = al((size_t)n * 8);
+  const size_t b_desc = orbfe_al256((size_t)n * 32), b_i = orbfe_al256((size_t)n * 4 + 4), b_d = orbfe_al256((size_t)n * 8);
   const size_t need = b_desc + 4 * b_i + b_d + 256;
   if (need > v->scratch_bytes) {
     hipFree(v->d_scratch);

@@ -33,6 +33,7 @@ def test_every_rgb_triple(ext, all_triples, mode, rgb):
     import torch
     img, d_img = all_triples
     d_out = torch.zeros((1, 4096, 4096), dtype=torch.uint8, device="cuda")
+    torch.cuda.current_stream().synchronize()  # the fill ran on torch's stream, the call runs on the handle's
     ext.to_gray_batch(d_img, d_out, rgb=rgb, gray_mode=mode)
     torch.cuda.synchronize()
     got = d_out[0].cpu().numpy()
@@ -62,6 +63,7 @@ def test_small_widths_unaligned_pitches_and_padding(ext, cols, channels):
     for mode in (R.GRAY_SHIFT15, R.GRAY_SHIFT14):
         for rgb in (True, False):
             d_dst = torch.full((2 + n * dstride,), SENTINEL, dtype=torch.uint8, device="cuda")
+            torch.cuda.current_stream().synchronize()  # the fill ran on torch's stream, the call runs on the handle's
             ext.to_gray_batch(torch.as_strided(d_src, (n, rows, cols, channels), (sstride, spitch, channels, 1), 1),
                               torch.as_strided(d_dst, (n, rows, cols), (dstride, dpitch, 1), 2), rgb=rgb,
                               gray_mode=mode)

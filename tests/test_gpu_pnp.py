@@ -114,6 +114,42 @@ def test_batch_of_three_and_one_unlaunched():
     batch.close()
 
 
+def test_handles_filled_to_every_bound():
+    """Two solvers with n == max_corr and n_hyp == max_hyp on a handle made for exactly two: every byte of its
+    buffers and of the refinement workspace is planned. Bit for bit what each solver gives alone on a fresh
+    handle with generous bounds."""
+    from orb_slam2_2021_amd import PnPBatch, PnPsolver
+    from pnp_scenes import Scene, draws
+
+    def snapshot(s):
+        arrays = (s.n_inliers, s.inlier_words, s.r, s.t, s.tcw, s.n_chosen, s.flags, s.records, s.refined_inliers,
+                  s.refined_words, s.refined_r, s.refined_t, s.refined_tcw, s.refined_n_chosen, s.refined_flags)
+        return [np.array(a).copy() for a in arrays] + [dict(s.found)]
+
+    solvers = []
+    for seed in (43, 44):
+        sc = Scene(65, seed=seed, noise=0.3, outliers=0.0)
+        s = PnPsolver(sc.p3dw, sc.p2d, sc.sigma2, sc.k)
+        s.SetRansacParameters(0.99, 10, 300, 4, 0.3, 5.991)
+        s.set_draws(draws(65, 3, seed))
+        solvers.append(s)
+    full = PnPBatch(max_solvers=2, max_corr=65, max_hyp=3)
+    full.solve(solvers)
+    together = [snapshot(s) for s in solvers]
+    full.close()
+    assert all(s.n_evaluated == 3 and s.inlier_words.shape == (3, 2) for s in solvers)
+    assert all(s.n_records >= 1 and int(s.refined_inliers.max()) > 19 for s in solvers)  # the workspace was used
+    for s, want in zip(solvers, together):
+        alone = PnPBatch(max_solvers=4, max_corr=320, max_hyp=300)
+        alone.solve([s])
+        got = snapshot(s)
+        for a, b in zip(got[:-1], want[:-1]):
+            assert a.shape == b.shape
+            same_bits(a, b, "alone against the full handle")
+        assert got[-1] == want[-1]
+        alone.close()
+
+
 def test_find_and_scatter_through_key_point_indices():
     from orb_slam2_2021_amd import PnPsolver
     sc, params, d = case("h24")

@@ -40,6 +40,7 @@ def test_hand_built_maps(ext):
         assert same_entries(rectify_entries_host(m1, m2, (scols, srows)), want_e)
         d_src = torch.from_numpy(src).cuda().unsqueeze(0)
         d_dst = torch.full((2,) + m1.shape, SENTINEL, dtype=torch.uint8, device="cuda")
+        torch.cuda.current_stream().synchronize()  # the fill ran on torch's stream, the call runs on the handle's
         rect.rectify_batch((d_src, d_src), d_dst)
         torch.cuda.synchronize()
         got = d_dst.cpu().numpy()
@@ -80,6 +81,7 @@ def test_small_widths_unaligned_pitches_and_padding(ext, cols, channels):
                 shape = (2 * n, row1 - row0, cols) + ((oc,) if oc != 1 else ())
                 strides = (dstride, dpitch, oc) + ((1,) if oc != 1 else ())
                 d_dst = torch.full((2 + 2 * n * dstride,), SENTINEL, dtype=torch.uint8, device="cuda")
+                torch.cuda.current_stream().synchronize()  # the fill ran on torch's stream, the call runs on the handle's
                 rect.rectify_batch(sview, torch.as_strided(d_dst, shape, strides, 2), rows=(row0, row1),
                                    gray_out=gray_out, rgb=rgb, gray_mode=mode)
                 torch.cuda.synchronize()
@@ -115,6 +117,7 @@ def test_arducam_cameras_at_vga(ext, vga_source):
     with StereoRectifier(ext, A["left"], A["right"], (640, 480)) as rect:
         d_src = torch.from_numpy(vga_source).cuda().unsqueeze(0)
         d_dst = torch.zeros((2, 400, 640), dtype=torch.uint8, device="cuda")
+        torch.cuda.current_stream().synchronize()  # the fill ran on torch's stream, the call runs on the handle's
         rect.rectify_batch(d_src, d_dst, rows=(0, 400), rgb=bool(A["rgb"]))
         torch.cuda.synchronize()
         got = d_dst.cpu().numpy()
@@ -141,6 +144,7 @@ def test_a_calibration_that_leaves_the_source(ext, vga_source):
     with StereoRectifier(ext, cam, cam4, S["size"], S["src_size"]) as rect:
         d_src = torch.from_numpy(src).cuda().unsqueeze(0)
         d_dst = torch.zeros((2, 480, 640, 3), dtype=torch.uint8, device="cuda")
+        torch.cuda.current_stream().synchronize()  # the fill ran on torch's stream, the call runs on the handle's
         rect.rectify_batch(d_src, d_dst, gray_out=False)
         torch.cuda.synchronize()
         got = d_dst.cpu().numpy()

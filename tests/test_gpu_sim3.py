@@ -328,6 +328,31 @@ def test_chain_into_search_by_sim3(batch):
     batch_big.close()
 
 
+# ---- a handle with no room to spare ---------------------------------------------------------------------
+@pytest.mark.parametrize("supplied", [False, True], ids=["draws", "hypotheses"])
+def test_handles_filled_to_every_bound(require_gpu, supplied):
+    """Two solvers with n == max_corr and n_hyp == max_hyp on a handle made for exactly two: every byte of its
+    buffers is planned. Bit for bit what each solver gives alone on a fresh handle with generous bounds."""
+    solvers = []
+    for seed in (91, 96):
+        sc = Scene(65, seed=seed, scale=1.1, outlier_frac=0.1, k2=K_OTHER)
+        g, r = make_pair(sc, False, 20, 300, draws(65, 3, seed=seed))
+        if supplied:
+            g.set_hypotheses(np.stack([h["T12"] for h in r.hyp]), np.stack([h["T21"] for h in r.hyp]))
+        solvers.append(g)
+    full = Sim3Batch(max_solvers=2, max_corr=65, max_hyp=3)
+    full.solve(solvers)
+    together = [snapshot(g) for g in solvers]
+    full.close()
+    assert all(g.n_evaluated == 3 and g.inlier_words.shape == (3, 2) for g in solvers)
+    assert all(int(g.n_inliers.max()) > 20 and g.inliers_of(2)[64] for g in solvers)  # bits in both mask words
+    for g, want in zip(solvers, together):
+        alone = Sim3Batch(max_solvers=4, max_corr=320, max_hyp=300)
+        alone.solve([g])
+        assert same_snapshot(snapshot(g), want)
+        alone.close()
+
+
 def test_excused_budget():
     """Last: at most 1 hypothesis in 10,000 of this run was excused by the midpoint rule."""
     print(f"compared {COMPARED[0]} hypotheses, excused {len(EXCUSED)}: {EXCUSED}")
